@@ -1,7 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the Chamfer3D / EMD hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--eager] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--eager] [--no-cpu]
+
+A plain run does what the headline figure needs and no more: it sets up,
+warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the result line (metric, value, unit,
+ms_per_step, the launch form).  --full adds everything measured beside the
+headline: the per-kernel and roofline figures (timed in runs of their own),
+the other forms of the loss collective at N>1, the side legs (ICP, the
+caller's call sequences, config 5, EMD) and the CPU baseline; the --no-*,
+--side-legs switches choose among those and mean nothing without --full.
+--dump-outputs DIR writes what the timed path computed in its last timed step,
+the arrays its caller receives (dist1, dist2, idx1, idx2, loss, grad_xyz1,
+grad_xyz2), as DIR/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy); the
+clouds are seeded, so two builds run with the same arguments can be compared
+output for output.
 
 One step = one pass of the hot path over one synthetic batch, exactly as a
 training step of train.py:162-176 drives it: Chamfer3D forward (both
@@ -21,8 +35,8 @@ at the driver's K = 20 (tools/ab_launch_form.py,
 profiles/r06/ab_launch_form_r06c.txt); --eager times the Python wrapper.  The
 GPU-side time of the timed region (HIP events at its edges, on the kernel's
 stream) is the dominant kernel's duration in `roofline`.
-Order: the headline's W warmup steps and K timed steps first, then the legs
-reported beside it (ICP, the unchanged caller's call sequence, config 5, EMD;
+Order (--full): the headline's W warmup steps and K timed steps first, then the
+legs reported beside it (ICP, the unchanged caller's call sequence, config 5, EMD;
 side_legs), then the CPU baseline.  --side-legs first runs those legs before
 the warmup instead: not faster (same box, profiles/r05/bench_side_legs_r05o.txt).
 
@@ -103,6 +117,12 @@ def parse(argv=None):
                    help="ranks (one per GPU); default: WORLD_SIZE under torchrun, else 1")
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what is reported beside the headline: per-kernel and roofline figures, the "
+                        "other forms of the loss collective (N>1), the side legs and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs (dist1, dist2, idx1, idx2, "
+                        "loss, grad_xyz1, grad_xyz2) as DIR/<name>.npy, float32")
     p.add_argument("--eager", action="store_true", help="no hipGraph capture (Python wrapper per step)")
     p.add_argument("--graph", action="store_true",
                    help="(the default form; kept for old command lines)")
@@ -884,6 +904,23 @@ def side_legs(args, dev, rank, world):
     return side
 
 
+DUMP_NAMES = ("dist1", "dist2", "idx1", "idx2", "loss", "grad_xyz1", "grad_xyz2")
+
+
+def dump_outputs(path, step, slot, rank):
+    """--dump-outputs: what the timed path's caller receives from its last
+    timed step -- both directions' squared distances and nearest indices, the
+    loss row that step wrote (mean(dist1), mean(dist2), their sum; summed over
+    ranks at N>1) and both clouds' gradients -- as float32 .npy files (1.3 MB
+    in all; the indices are below 2^24, so float32 holds them exactly)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tensors = (step.d1, step.d2, step.i1, step.i2, step.loss[slot], step.gx1, step.gx2)
+    for name, t in zip(DUMP_NAMES, tensors):
+        file = name + (".npy" if rank == 0 else f"_rank{rank}.npy")
+        np.save(os.path.join(path, file), t.detach().cpu().numpy().astype(np.float32))
+
+
 def main(argv=None):
     args = parse(argv)
     # decided before any GPU call: a process that has initialised the GPU
@@ -922,6 +959,7 @@ def main(argv=None):
     run_steps, mode, capture_error = run_eager, "eager, one all-reduce per step" if multi else "eager", None
     g_one = None
     graph_info = None
+    last_slot = 0  # the row of step.loss the last timed step writes (--dump-outputs)
     if not args.eager:
         s = torch.cuda.Stream(dev)
         s.wait_stream(torch.cuda.current_stream(dev))
@@ -944,6 +982,7 @@ def main(argv=None):
                     for _ in range(k % per):
                         g_one.replay()
                 mode = f"hipgraph ({per} steps per graph; N>1 adds each step's all-reduce to the same graph)"
+                last_slot = 0 if args.steps % per else per - 1
             else:
                 go = step.launcher()
 
@@ -987,13 +1026,14 @@ def main(argv=None):
                         g_ar_one.replay()
                 mode = (f"hipgraph ({per} steps per graph, each step's loss all-reduced over RCCL inside "
                         "the graph on a side stream)")
+                last_slot = 0 if args.steps % per else per - 1
             else:
                 def run_steps(k):
                     for _ in range(k):
                         g_one.replay()
                         step.reduce_losses(1)
                 mode = "one-step hipgraph replay + eager all-reduce of the step's loss, every step"
-        side = side_legs(args, dev, rank, world) if args.side_legs == "first" else {}
+        side = side_legs(args, dev, rank, world) if args.full and args.side_legs == "first" else {}
         if multi or not args.c_loop:
             g_tail = g_one if not multi else (g_ar_one if g_ar_many is not None else None)
             graph_info = warm_graphs(g_many, g_tail, per, args.warmup, args.steps, run_steps, dev, world)
@@ -1007,42 +1047,17 @@ def main(argv=None):
                           "warmup_steps_run": args.warmup}
 
     if args.eager:
-        side = side_legs(args, dev, rank, world) if args.side_legs == "first" else {}
+        side = side_legs(args, dev, rank, world) if args.full and args.side_legs == "first" else {}
         run_steps(args.warmup)
         torch.cuda.synchronize(dev)
     gpu_t = []
     t = time_region(lambda: run_steps(args.steps), 1, dev, world, gpu=gpu_t)
-    if graph_info is not None and g_many is not None:
-        # a steady replay of the `per`-step graph after the timed region (with
-        # --graph, compare with the first replay, which warmup paid)
-        graph_info["steady_replay_us"] = time_region(g_many.replay, 1, dev, world) * 1e6
-        graph_info["steady_replay_us_per_step"] = graph_info["steady_replay_us"] / per
+    if args.dump_outputs:
+        # first thing after the timed steps: the buffers hold the last timed step's results
+        dump_outputs(args.dump_outputs, step, last_slot, rank)
     pairs_per_step = 2 * B * N * M
     value = world * args.steps * pairs_per_step / t
     ms = t * 1000.0 / args.steps
-
-    # dominant kernel: the step's Chamfer forward (fused-loss) launch, timed on its stream
-    fwd_us = kernel_avg_us(lambda: pcm_hip.chamfer_forward_loss(
-        step.xyz1, step.xyz2, step.d1, step.d2, step.i1, step.i2, step.loss[0], step.ws), 200, dev)
-    bwd_us = kernel_avg_us(lambda: pcm_hip.chamfer_backward(step.xyz1, step.xyz2, step.g1, step.g2,
-                                                            step.i1, step.i2, step.gx1, step.gx2),
-                           200, dev)
-    fwd_tflops = pairs_per_step * FLOP_PER_PAIR / (fwd_us * 1e-6) / 1e12
-    # the dominant kernel's duration: HIP events on the kernel's stream over
-    # the timed region itself (back-to-back launches: the kernel plus its
-    # launch boundary); the 200-launch graph average beside it
-    region_us = gpu_t[0] * 1e6 / args.steps
-    if step.fused:
-        dom_kernel, dom_bytes = FUSED_KERNEL, FUSED_BYTES
-        graph_kernel_us = kernel_avg_us(lambda: step(0), 200, dev)
-        sustained_us = sustained_kernel_us(lambda: step(0), dev)
-        dom_us = region_us if not (args.eager or multi) else graph_kernel_us
-    else:
-        dom_kernel, dom_bytes, dom_us = FWD_KERNEL, FWD_BYTES, fwd_us
-        graph_kernel_us = fwd_us
-        sustained_us = None
-    dom_tflops = pairs_per_step * FLOP_PER_PAIR / (dom_us * 1e-6) / 1e12
-    traffic = pmc_bytes(dom_kernel)
     out = {
         "metric": "Chamfer3D fwd+bwd point-pairs/sec @ B=32 N=M=1024; EMD iters/sec",
         "value": value,
@@ -1061,6 +1076,59 @@ def main(argv=None):
                    "global_batch": world * B, "parallelism": f"dp{world} (batch-sharded)",
                    "launch": mode, "dist_backend": args.dist_backend if multi else None,
                    **({"tune_variant": args.tune_variant} if args.tune_variant is not None else {})},
+    }
+    if graph_info is not None:
+        out["graph"] = graph_info
+        out["warmup_steps_run"] = graph_info["warmup_steps_run"]
+    if capture_error is not None:
+        out["config"]["allreduce_capture_error"] = capture_error
+    if args.full:
+        out.update(side)  # the side legs, had they run first
+        full_report(out, args, step, dev, rank, world, multi, per, ms, gpu_t[0], g_one,
+                    g_many if graph_info is not None else None)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if multi:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_report(out, args, step, dev, rank, world, multi, per, ms, region_s, g_one, g_many):
+    """--full: what is measured beside the headline, added to the result line
+    `out` after the timed region: per-kernel and roofline figures (runs of
+    their own), the other forms of the loss collective (N>1), the side legs
+    unless they ran first, and the CPU baseline."""
+    graph_info = out.get("graph")
+    if graph_info is not None and g_many is not None:
+        # a steady replay of the `per`-step graph after the timed region (with
+        # --graph, compare with the first replay, which warmup paid)
+        graph_info["steady_replay_us"] = time_region(g_many.replay, 1, dev, world) * 1e6
+        graph_info["steady_replay_us_per_step"] = graph_info["steady_replay_us"] / per
+    pairs_per_step = 2 * B * N * M
+
+    # dominant kernel: the step's Chamfer forward (fused-loss) launch, timed on its stream
+    fwd_us = kernel_avg_us(lambda: pcm_hip.chamfer_forward_loss(
+        step.xyz1, step.xyz2, step.d1, step.d2, step.i1, step.i2, step.loss[0], step.ws), 200, dev)
+    bwd_us = kernel_avg_us(lambda: pcm_hip.chamfer_backward(step.xyz1, step.xyz2, step.g1, step.g2,
+                                                            step.i1, step.i2, step.gx1, step.gx2),
+                           200, dev)
+    fwd_tflops = pairs_per_step * FLOP_PER_PAIR / (fwd_us * 1e-6) / 1e12
+    # the dominant kernel's duration: HIP events on the kernel's stream over
+    # the timed region itself (back-to-back launches: the kernel plus its
+    # launch boundary); the 200-launch graph average beside it
+    region_us = region_s * 1e6 / args.steps
+    if step.fused:
+        dom_kernel, dom_bytes = FUSED_KERNEL, FUSED_BYTES
+        graph_kernel_us = kernel_avg_us(lambda: step(0), 200, dev)
+        sustained_us = sustained_kernel_us(lambda: step(0), dev)
+        dom_us = region_us if not (args.eager or multi) else graph_kernel_us
+    else:
+        dom_kernel, dom_bytes, dom_us = FWD_KERNEL, FWD_BYTES, fwd_us
+        graph_kernel_us = fwd_us
+        sustained_us = None
+    dom_tflops = pairs_per_step * FLOP_PER_PAIR / (dom_us * 1e-6) / 1e12
+    traffic = pmc_bytes(dom_kernel)
+    out.update({
         "roofline": {"bound": "valu", "kernel": dom_kernel,
                      "achieved": dom_tflops, "peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": dom_tflops / FP32_VALU_PEAK_TFLOPS, "traffic": traffic,
@@ -1092,14 +1160,9 @@ def main(argv=None):
                        "bwd_achieved_gbs": BWD_BYTES / (bwd_us * 1e-6) / 1e9,
                        "bwd_algorithmic_bytes": BWD_BYTES, "bwd_traffic": pmc_bytes(BWD_KERNEL),
                        "step_us": fwd_us + bwd_us},
-    }
-    if graph_info is not None:
-        out["graph"] = graph_info
-        out["warmup_steps_run"] = graph_info["warmup_steps_run"]
+    })
     out["roofline"]["step_minus_kernel_us"] = ms * 1000.0 - dom_us
     out["roofline_executed"] = chamfer_executed_roofline(dom_kernel, dom_us)
-    if capture_error is not None:
-        out["config"]["allreduce_capture_error"] = capture_error
     if multi:
         # the other forms of the loss collective, beside the headline
         per_rank_us = torch.tensor([dom_us], device=dev, dtype=torch.float64)
@@ -1132,19 +1195,13 @@ def main(argv=None):
                 "ms_per_step": t_b * 1000.0 / kb,
                 "value": world * kb * pairs_per_step / t_b}
     if args.side_legs == "last":
-        side = side_legs(args, dev, rank, world)
-    out.update(side)
+        out.update(side_legs(args, dev, rank, world))
     if "reference_call" in out:
         out["reference_call"]["graph_vs_fused_step"] = out["reference_call"]["graph_us_per_step"] / (ms * 1000.0)
     if "training_call" in out:
         out["training_call"]["graph_vs_fused_step"] = out["training_call"]["graph_us_per_step"] / (ms * 1000.0)
     if rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if multi:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

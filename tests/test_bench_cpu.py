@@ -46,6 +46,14 @@ def test_spawn_command_is_the_driver_form():
     assert cmd[-4:] == ["--gpus", "4", "--steps", "20"]
 
 
+def test_plain_run_is_the_default():
+    """Without --full only the headline is measured; --dump-outputs names a directory."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+
+
 def test_mismatch_fails_before_any_gpu_work():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "3"], env=env,

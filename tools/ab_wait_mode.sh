@@ -13,7 +13,7 @@ for r in 1 2; do
       active) E="ROC_ACTIVE_WAIT_TIMEOUT=1000" ;;
       poll) E="HSA_ENABLE_INTERRUPT=0" ;;
     esac
-    env $E timeout -k 10 240 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_$mode$r.json" 2> "$O/bench_$mode$r.err" || exit 1
+    env $E timeout -k 10 240 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_$mode$r.json" 2> "$O/bench_$mode$r.err" || exit 1
     python3 -c "
 import json,sys; d=json.load(open('$O/bench_$mode$r.json')); r=d['roofline']
 print('%-8s step %.3f us  kernel %.3f us  step-kernel %.3f us' % ('$mode', d['ms_per_step']*1e3, r['kernel_us'], d['ms_per_step']*1e3 - r['kernel_us']))" | tee -a "$O/wait_mode.txt"

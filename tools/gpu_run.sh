@@ -2,10 +2,10 @@
 # in order, each under its own time limit, output under gpurun_out/TAG/, and
 # stops at the first failing step (no GPU work after a fault or a time-out).
 # Steps:
-#   bench      python bench.py --gpus 1 --steps 20 --warmup 5 (the driver's exact N=1 command)
-#   benchlong  python bench.py (200 steps, 20 warmup)
-#   gloo2      bench.py --gpus 2 --dist-backend gloo (two ranks on one GPU)
-#   forcedist  bench.py --force-dist (one-rank RCCL: the captured per-step collective)
+#   bench      python bench.py --gpus 1 --steps 20 --warmup 5 --full (the standard N=1 command, every leg)
+#   benchlong  python bench.py --full (200 steps, 20 warmup)
+#   gloo2      bench.py --gpus 2 --dist-backend gloo --full (two ranks on one GPU)
+#   forcedist  bench.py --force-dist --full (one-rank RCCL: the captured per-step collective)
 #   pytest     pytest -m gpu (every GPU test)
 #   pytest:F   pytest -m gpu on tests/F only
 #   smoke      __graft_entry__.smoke()
@@ -34,14 +34,15 @@ shift
 O=gpurun_out/$TAG
 mkdir -p "$O"
 export TMPDIR=/tmp
+ROOT=$PWD  # the repository root: the steps run from it
 for S in "$@"; do
     echo "[gpu_run] $S $(date +%T)"
     case "$S" in
-    bench) timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err" ;;
-    benchlong) timeout -k 10 600 python -u bench.py > "$O/benchlong.json" 2> "$O/benchlong.err" ;;
-    gloo2) timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-cpu \
+    bench) timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err" ;;
+    benchlong) timeout -k 10 600 python -u bench.py --full > "$O/benchlong.json" 2> "$O/benchlong.err" ;;
+    gloo2) timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --full --no-cpu \
                --no-emd --no-dense --no-icp --no-ref-call > "$O/gloo2.json" 2> "$O/gloo2.err" ;;
-    forcedist) timeout -k 10 300 python -u bench.py --force-dist --steps 50 --warmup 5 --no-cpu --no-emd \
+    forcedist) timeout -k 10 300 python -u bench.py --force-dist --steps 50 --warmup 5 --full --no-cpu --no-emd \
                --no-dense --no-icp --no-ref-call > "$O/forcedist.json" 2> "$O/forcedist.err" ;;
     pytest) timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
                > "$O/pytest.txt" 2>&1 ;;
@@ -49,9 +50,9 @@ for S in "$@"; do
                --timeout-method thread > "$O/pytest_${S#pytest:}.txt" 2>&1 ;;
     smoke) timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' \
                > "$O/smoke.txt" 2>&1 ;;
-    rocprof) (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/prof" \
-               -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu > "$GRAFT_REPO_ROOT/$O/rocprof_bench.json" \
-               2> "$GRAFT_REPO_ROOT/$O/rocprof.err") ;;
+    rocprof) (cd "$TMPDIR" && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$ROOT/$O/prof" \
+               -o run --output-format csv -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --full --no-cpu \
+               > "$ROOT/$O/rocprof_bench.json" 2> "$ROOT/$O/rocprof.err") ;;
     abc) AB_VARIANTS=${AB_VARIANTS:-11,15} timeout -k 10 600 python -u tools/ab_chamfer.py > "$O/ab_chamfer.txt" 2>&1 &&
          AB_VARIANTS=${AB_VARIANTS:-11,15} timeout -k 10 600 python -u tools/ab_chamfer.py >> "$O/ab_chamfer.txt" 2>&1 ;;
     abcc) AB_COLD=${AB_COLD:-0.3} AB_VARIANTS=${AB_VARIANTS:-11,15} timeout -k 10 600 python -u tools/ab_chamfer.py \
@@ -108,7 +109,7 @@ for S in "$@"; do
                  > "$GRAFT_REPO_ROOT/$O/tct_$f.log" 2>&1) || exit 1
          done ;;
     benchab) for i in 1 2; do for o in first last; do
-               timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --side-legs $o \
+               timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full --side-legs $o \
                    > "$O/bench_${o}_$i.json" 2> "$O/bench_${o}_$i.err" || exit 1; done; done ;;
     gap) timeout -k 10 300 python -u tools/ab_bench_gap.py > "$O/ab_bench_gap.txt" 2>&1 &&
          timeout -k 10 300 python -u tools/ab_bench_gap.py >> "$O/ab_bench_gap.txt" 2>&1 ;;
@@ -124,11 +125,11 @@ for S in "$@"; do
                  > "$GRAFT_REPO_ROOT/$O/tctg_$f.log" 2>&1) || exit 1
          done ;;
     benchv) for r in 1 2 3; do for v in ${BENCH_VARIANTS:-15 14 7}; do
-               timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-emd --no-dense \
+               timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-emd --no-dense \
                    --no-icp --no-ref-call --tune-variant $v >> "$O/bench_variants.jsonl" 2>> "$O/bench_variants.err" || exit 1
            done; done ;;
     bench3) for r in 1 2 3; do
-              timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench_$r.json" 2> "$O/bench_$r.err" || exit 1
+              timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench_$r.json" 2> "$O/bench_$r.err" || exit 1
             done ;;
     pmcf) (cd /tmp && timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE -d "$GRAFT_REPO_ROOT/$O/pmcf_fetch" -o fetch \
                --output-format csv -- python3 "$GRAFT_REPO_ROOT/tools/profile_kernels.py" fused ${PMC_VARIANTS:-7,16} \

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 PROG="tools/profile_kernels.py"
 rocprofv3 -L > "$OUT/counters_list.txt" 2>&1 || true
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o bench --output-format csv \
-    -- python3 bench.py --steps 50 --warmup 10 --no-cpu > "$OUT/kt_bench.log" 2>&1
+    -- python3 bench.py --steps 50 --warmup 10 --full --no-cpu > "$OUT/kt_bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt_eager" -o eager --output-format csv \
     -- python3 "$PROG" > "$OUT/kt_eager.log" 2>&1
 timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv \
