@@ -37,6 +37,7 @@ EXPORTED = (
     "pcm_chamfer_loss_grad", "pcm_chamfer_forward_layout", "pcm_chamfer_backward_layout",
     "pcm_chamfer_backward_strided", "pcm_chamfer_loss_grad_layout", "pcm_chamfer_loss_grad_rescale",
     "pcm_chamfer_loss_grad_steps",
+    "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -169,6 +170,12 @@ def _open(path):
         L.pcm_chamfer_loss_grad_steps.restype = ci
         L.pcm_chamfer_loss_grad_steps.argtypes = [ci, vp, vp, ci, ci, ci, cf, cf, vp, vp, vp, vp, vp, vp, vp, vp,
                                                   cs, vp]
+    if hasattr(L, "pcm_chamfer_eval"):  # absent from A/B builds of older sources
+        L.pcm_chamfer_eval_workspace_bytes.restype = cs
+        L.pcm_chamfer_eval_workspace_bytes.argtypes = [ci, ci, ci, ci]
+        for fn in (L.pcm_chamfer_eval, L.pcm_chamfer_eval_f16):
+            fn.restype = ci
+            fn.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -766,6 +773,56 @@ def chamfer_backward(xyz1, xyz2, graddist1, graddist2, idx1, idx2, gradxyz1, gra
         _check(getattr(load_library(), fn)(
             _ptr(xyz1), _ptr(xyz2), b, n, m, _ptr(graddist1), _ptr(graddist2), _ptr(idx1),
             _ptr(idx2), _ptr(gradxyz1), _ptr(gradxyz2), _stream(dev)), fn)
+
+
+EVAL_MAX_THRESHOLDS = 8  # csrc/chamfer_eval.hip kEvalMaxTh
+
+
+def chamfer_eval_workspace(dev: torch.device, b: int, n: int, m: int, nth: int) -> torch.Tensor:
+    """Scratch for chamfer_eval (the workgroups' partial records): ONE buffer
+    per (device, current stream), grown when a larger problem needs more; its
+    content on entry is irrelevant and it holds nothing between calls."""
+    need = max(int(load_library().pcm_chamfer_eval_workspace_bytes(b, n, m, nth)), 1)
+    key = ("eval", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def chamfer_eval(xyz1, xyz2, thresholds, mean_dist, counts, scores, batch_scores=None, workspace=None) -> None:
+    """pcm_chamfer_eval (float32 clouds) or pcm_chamfer_eval_f16 (float16) on
+    contiguous [B,N,3]/[B,M,3] device tensors: for the 1..8 squared-distance
+    `thresholds` (host floats) mean_dist [B,2] float32, counts [B,T,2] int32,
+    scores [B,T,3] float32 = (F-score, p_x, p_y) and, when given, batch_scores
+    [T,3] float32 (include/pcm.h).  Two launches; no per-point output."""
+    tensors = (xyz1, xyz2, mean_dist, counts, scores) + (() if batch_scores is None else (batch_scores,))
+    dev = _require_device(*tensors)
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    th = [float(t) for t in thresholds]
+    nth = len(th)
+    if not 1 <= nth <= EVAL_MAX_THRESHOLDS:
+        raise ValueError(f"chamfer_eval takes 1..{EVAL_MAX_THRESHOLDS} thresholds (got {nth})")
+    f16 = _cloud_kind(xyz1, xyz2) == "f16"
+    if xyz2.shape[0] != b or xyz1.shape[2] != 3 or xyz2.shape[2] != 3:
+        raise ValueError("chamfer_eval takes clouds [B, N, 3] and [B, M, 3]")
+    if not (xyz1.is_contiguous() and xyz2.is_contiguous()):
+        raise ValueError("chamfer_eval takes contiguous clouds")
+    for t, shape, dtype in ((mean_dist, (b, 2), torch.float32), (counts, (b, nth, 2), torch.int32),
+                            (scores, (b, nth, 3), torch.float32)) + (
+                                () if batch_scores is None else ((batch_scores, (nth, 3), torch.float32),)):
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"chamfer_eval output must be contiguous {dtype} of shape {shape}")
+    th_arr = (ctypes.c_float * nth)(*th)
+    fn = "pcm_chamfer_eval_f16" if f16 else "pcm_chamfer_eval"
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = chamfer_eval_workspace(dev, b, n, m, nth)
+        _check(getattr(load_library(), fn)(
+            _ptr(xyz1), _ptr(xyz2), b, n, m, th_arr, nth, _ptr(mean_dist), _ptr(counts), _ptr(scores),
+            _ptr(batch_scores), _ptr(workspace), workspace.numel(), _stream(dev)), fn)
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

@@ -12,6 +12,11 @@ Surface kept from utils/metrics.py:10-109, so testnet.py-style callers work unch
     the auction with eps 0.005 and 50 iterations (utils/metrics.py:49-53).
   * ``Metrics._get_chamfer_distance``: 100 * (mean(dist1) + mean(dist2))
     (utils/metrics.py:56-60).
+  * ``Metrics._get_fscore``: the batch-mean F-score of loss/loss_.py:122-140 at the
+    squared-distance threshold ``EVAL_FSCORE_THRESHOLD`` (its default, 1e-4), in
+    [0, 1], greater is better. Extension: the reference's table has no such item,
+    so the ``F-Score`` descriptor is present but **disabled**; ``Metrics.names()``
+    and ``Metrics.get()`` stay the reference's two until a caller enables it.
   * ``Metrics(metric_name, values)``, where ``values`` is a list, or a dict keyed
     by metric name (unknown names are skipped with a warning). Also
     ``state_dict()``, ``repr()`` and ``better_than(other)``.
@@ -32,12 +37,15 @@ for _sub in ("emd", "chamfer3D"):
     if _path not in sys.path:
         sys.path.append(_path)
 from dist_chamfer_3D import chamfer_3DDist  # noqa: E402
+from eval_chamfer_3D import chamfer_3DEval  # noqa: E402
 import emd_module  # noqa: E402
 
 # the evaluation call setting of utils/metrics.py:51 (the training loss uses 0.05 / 3000)
 EVAL_EMD_EPS = 0.005
 EVAL_EMD_ITERS = 50
 _SCALE = 100.0
+# fscore's default threshold (loss/loss_.py:122), a squared distance
+EVAL_FSCORE_THRESHOLD = 1e-4
 
 _log = logging.getLogger(__name__)
 
@@ -53,6 +61,9 @@ class Metrics(object):
     ITEMS = [
         _descriptor('EMD_distance', '_get_emd_distance', emd_module.emdModule()),
         _descriptor('ChamferDistance', '_get_chamfer_distance', chamfer_3DDist()),
+        # not in the reference's table: off unless a caller enables it
+        dict(name='F-Score', enabled=False, eval_func='_get_fscore',
+             eval_object=chamfer_3DEval((EVAL_FSCORE_THRESHOLD,)), is_greater_better=True, init_value=0),
     ]
 
     # ---- class-level evaluation -------------------------------------------------
@@ -85,6 +96,11 @@ class Metrics(object):
     def _get_chamfer_distance(cls, pred, gt):
         d1, d2, _, _ = cls._module('_get_chamfer_distance')(pred, gt)
         return float(d1.mean() + d2.mean()) * _SCALE
+
+    @classmethod
+    def _get_fscore(cls, pred, gt):
+        # batch_means[0] = (F-score, precision, recall) at the one threshold
+        return float(cls._module('_get_fscore').batch_means(pred, gt)[0, 0])
 
     # ---- a recorded set of metric values ---------------------------------------
     def __init__(self, metric_name, values):

@@ -249,6 +249,55 @@ int pcm_chamfer_forward_ws_f16(const uint16_t *xyz1, const uint16_t *xyz2, int b
                                float *dist1, float *dist2, int32_t *idx1, int32_t *idx2,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * One-pass Chamfer evaluation (extension): the F-score, precision and recall of
+ * loss/loss_.py:122-140 (fscore) at up to eight squared-distance thresholds,
+ * and the per-cloud mean nearest-neighbour distances, without the B x N x M
+ * float64 distance matrix of batch_NN_loss (:93-109), without argmins and
+ * without any per-point output.  It replaces fscore's compare / cast / mean /
+ * arithmetic / NaN fix-up (:132-138) as well: two launches in all.
+ *
+ * Contract: for every batch element and both directions the per-point value is
+ * exactly the dist1[b,j] / dist2[b,k] pcm_chamfer_forward would produce -- for
+ * finite inputs the minimum of the pinned fmaf(dz,dz,fmaf(dy,dy,dx*dx)) values
+ * (independent of the scan order, so no index is tracked); with non-finite
+ * coordinates the reference's 512-point tile rule decides, as there.
+ *   thresholds: HOST pointer to nth floats (1 <= nth <= 8, any order), read
+ *     during the call and passed to the kernel by value: no device-side
+ *     threshold buffer, so the call is capturable.
+ *   With c1 = #{j: dist1[b,j] < th[t]} and c2 = #{k: dist2[b,k] < th[t]}
+ *   (strict '<', loss_.py:132-133; a NaN distance is never counted):
+ *     counts[b,t,0] = c1, counts[b,t,1] = c2                       (int32)
+ *     p_x = (float)c1 / (float)n    share of xyz1's points within th of xyz2
+ *     p_y = (float)c2 / (float)m    share of xyz2's points within th of xyz1
+ *     f   = (c1 + c2 == 0) ? 0.f : ((2.f * p_y) * p_x) / (p_y + p_x)
+ *                                   (loss_.py:134-135: the 0/0 NaN becomes 0)
+ *     scores[b,t,:] = f, p_x, p_y
+ *     mean_dist[b,0] = sum_j dist1[b,j] / (float)n, mean_dist[b,1] = sum_k dist2[b,k] / (float)m
+ *   batch_scores (nullable) [nth,3]: loss_.py:136-138 -- the sequential fp32
+ *     sum over b = 0, 1, ... of scores[b,t,:], divided by (float)b.
+ *   fscore(X, Y, th) of the reference = batch_scores[0,0], [0,2], [0,1]
+ *   (its precision_1 is the mean over Y's points: p_y).
+ * Sums are formed in a fixed order (wave, workgroup, then each cloud's
+ * workgroups in ascending order): deterministic, no float atomics.
+ * Any n, m >= 1; b limited only by the grid (else PCM_ERR_UNSUPPORTED).
+ * PCM_ERR_INVALID_ARG before any device call for negative sizes, n == 0 or
+ * m == 0 with b > 0, nth outside 1..8, or a null cloud / threshold / output
+ * pointer with b > 0; PCM_ERR_WORKSPACE for a workspace that is NULL or
+ * shorter than pcm_chamfer_eval_workspace_bytes(b, n, m, nth); b == 0 is a
+ * no-op.  The workspace needs no initialisation and holds no state between
+ * calls; every output element is fully written.
+ * pcm_chamfer_eval_f16: IEEE binary16 clouds widened exactly, so every output
+ * is bit-identical to pcm_chamfer_eval on the widened clouds.
+ */
+size_t pcm_chamfer_eval_workspace_bytes(int b, int n, int m, int nth);
+int pcm_chamfer_eval(const float *xyz1, const float *xyz2, int b, int n, int m, const float *thresholds, int nth,
+                     float *mean_dist, int32_t *counts, float *scores, float *batch_scores, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int pcm_chamfer_eval_f16(const uint16_t *xyz1, const uint16_t *xyz2, int b, int n, int m, const float *thresholds,
+                         int nth, float *mean_dist, int32_t *counts, float *scores, float *batch_scores,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
 /* ---------------------------------------------------------------------- */
