@@ -38,6 +38,7 @@ EXPORTED = (
     "pcm_chamfer_backward_strided", "pcm_chamfer_loss_grad_layout", "pcm_chamfer_loss_grad_rescale",
     "pcm_chamfer_loss_grad_steps",
     "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
+    "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -176,6 +177,15 @@ def _open(path):
         for fn in (L.pcm_chamfer_eval, L.pcm_chamfer_eval_f16):
             fn.restype = ci
             fn.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_silhouette_forward"):  # absent from A/B builds of older sources
+        L.pcm_silhouette_forward.restype = ci
+        L.pcm_silhouette_forward.argtypes = [vp, ci, ci, ci, ci, ci, cf, vp, vp]
+        L.pcm_silhouette_backward.restype = ci
+        L.pcm_silhouette_backward.argtypes = [vp, ci, ci, ci, ci, ci, cf, vp, vp, vp]
+        L.pcm_proj_bce_workspace_bytes.restype = cs
+        L.pcm_proj_bce_workspace_bytes.argtypes = [ctypes.c_longlong]
+        L.pcm_proj_bce.restype = ci
+        L.pcm_proj_bce.argtypes = [vp, vp, ctypes.c_longlong, cf, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -823,6 +833,80 @@ def chamfer_eval(xyz1, xyz2, thresholds, mean_dist, counts, scores, batch_scores
         _check(getattr(load_library(), fn)(
             _ptr(xyz1), _ptr(xyz2), b, n, m, th_arr, nth, _ptr(mean_dist), _ptr(counts), _ptr(scores),
             _ptr(batch_scores), _ptr(workspace), workspace.numel(), _stream(dev)), fn)
+
+
+SILHOUETTE_MAX_GRID = 128  # include/pcm.h PCM_SILHOUETTE_MAX_GRID
+
+
+def _silhouette_args(xyz, layout, grid_h, grid_w, sigma_sq):
+    if xyz.dtype != torch.float32:
+        raise TypeError(f"the silhouette kernels take float32 clouds (got {xyz.dtype})")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError("the silhouette kernels take clouds [B, N, 3]")
+    if cloud_layout(xyz) != int(layout):
+        raise ValueError("the cloud is not in the layout given (pcm_hip.cloud_layout)")
+    return xyz.shape[0], xyz.shape[1], int(layout), int(grid_h), int(grid_w), float(sigma_sq)
+
+
+def silhouette_forward(xyz, layout, grid_h, grid_w, sigma_sq, sil) -> None:
+    """pcm_silhouette_forward: sil [B, grid_h, grid_w] float32 (contiguous) =
+    the Gaussian-splatted silhouette of the float32 cloud xyz [B, N, 3], given
+    as rows (layout 0) or as a view of channel planes (1, see cloud_layout)."""
+    dev = _require_device(xyz, sil)
+    b, n, lay, gh, gw, s2 = _silhouette_args(xyz, layout, grid_h, grid_w, sigma_sq)
+    if tuple(sil.shape) != (b, gh, gw) or sil.dtype != torch.float32 or not sil.is_contiguous():
+        raise ValueError(f"sil must be contiguous float32 of shape {(b, gh, gw)}")
+    with torch.cuda.device(dev):
+        _check(load_library().pcm_silhouette_forward(_ptr(xyz), b, n, lay, gh, gw, s2, _ptr(sil), _stream(dev)),
+               "pcm_silhouette_forward")
+
+
+def silhouette_backward(xyz, layout, grid_h, grid_w, sigma_sq, grad_sil, gradxyz) -> None:
+    """pcm_silhouette_backward: gradxyz (xyz's shape and layout) from grad_sil
+    [B, grid_h, grid_w] float32 (contiguous); gradxyz[..., 2] = 0."""
+    dev = _require_device(xyz, grad_sil, gradxyz)
+    b, n, lay, gh, gw, s2 = _silhouette_args(xyz, layout, grid_h, grid_w, sigma_sq)
+    if tuple(grad_sil.shape) != (b, gh, gw) or grad_sil.dtype != torch.float32 or not grad_sil.is_contiguous():
+        raise ValueError(f"grad_sil must be contiguous float32 of shape {(b, gh, gw)}")
+    if gradxyz.dtype != torch.float32 or gradxyz.shape != xyz.shape or cloud_layout(gradxyz) != lay:
+        raise ValueError("gradxyz must have the cloud's dtype, shape and layout")
+    with torch.cuda.device(dev):
+        _check(load_library().pcm_silhouette_backward(_ptr(xyz), b, n, lay, gh, gw, s2, _ptr(grad_sil),
+                                                      _ptr(gradxyz), _stream(dev)), "pcm_silhouette_backward")
+
+
+def proj_bce_workspace(dev: torch.device, count: int) -> torch.Tensor:
+    """Scratch for proj_bce (the workgroups' partial sums): ONE buffer per
+    (device, current stream), grown when a larger problem needs more; its
+    content on entry is irrelevant and it holds nothing between calls."""
+    need = max(int(load_library().pcm_proj_bce_workspace_bytes(count)), 1)
+    key = ("bce", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def proj_bce(pred, gt, w, loss_out, grad_pred=None, workspace=None) -> None:
+    """pcm_proj_bce on contiguous float32 device tensors pred, gt of one shape:
+    loss_out[0] = the mean 'bce_prob' term (loss/proj_loss.py:17-19, :43) and,
+    when given, grad_pred = its gradient with respect to pred."""
+    tensors = (pred, gt, loss_out) + (() if grad_pred is None else (grad_pred,))
+    dev = _require_device(*tensors)
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("proj_bce takes contiguous float32 tensors")
+    if pred.shape != gt.shape or (grad_pred is not None and grad_pred.shape != pred.shape):
+        raise ValueError("proj_bce takes pred, gt and grad_pred of one shape")
+    if loss_out.numel() < 1:
+        raise ValueError("loss_out needs one float")
+    count = pred.numel()
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = proj_bce_workspace(dev, count)
+        _check(load_library().pcm_proj_bce(_ptr(pred), _ptr(gt), count, float(w), _ptr(loss_out), _ptr(grad_pred),
+                                           _ptr(workspace), workspace.numel(), _stream(dev)), "pcm_proj_bce")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

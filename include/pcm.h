@@ -16,6 +16,10 @@
  *                         <- icp / nearest_neighbor / best_fit_transform
  *                            (utils/icp.py:68-118, :49-65, :4-46; numpy + sklearn
  *                            on the host in the reference, testnet.py:62-64)
+ *   pcm_silhouette_forward / _backward, pcm_proj_bce
+ *                         <- cont_proj (utils/projection.py:4-67) and the 'bce_prob'
+ *                            loss (loss/proj_loss.py:17-19, :43): torch ops in the
+ *                            reference, finetune.py:154-162
  *
  * Conventions:
  *   - all pointers are DEVICE pointers to contiguous row-major arrays:
@@ -297,6 +301,98 @@ int pcm_chamfer_eval(const float *xyz1, const float *xyz2, int b, int n, int m, 
 int pcm_chamfer_eval_f16(const uint16_t *xyz1, const uint16_t *xyz2, int b, int n, int m, const float *thresholds,
                          int nth, float *mean_dist, int32_t *counts, float *scores, float *batch_scores,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Projection loss (finetune.py:154-162)                                   */
+/* ---------------------------------------------------------------------- */
+
+/* Largest grid_h / grid_w of the silhouette entries (else PCM_ERR_UNSUPPORTED). */
+#define PCM_SILHOUETTE_MAX_GRID 128
+/* Longest sequential chain of float32 additions behind pcm_proj_bce's
+ * loss_out for any count <= 2^20 (see the summation order below). */
+#define PCM_PROJ_BCE_CHAIN 30
+
+/*
+ * Gaussian-splatted silhouette of a point cloud (extension): cont_proj of
+ * utils/projection.py:4-67, which materialises a B x N x H x W x 2 float32
+ * difference tensor, its exponential (apply_kernel, :97-108), a B x N x H x W
+ * product and a sum over N (on the CPU, utils/utils.py:232), as one launch
+ * that keeps nothing of size N x H x W anywhere.
+ *
+ * Contract.  Coordinate map, float32, as projection.py:20-21:
+ *     gx = ((px + 1.f) * (float)grid_h) / 2.f     (row index h: first coordinate)
+ *     gy = ((py + 1.f) * (float)grid_w) / 2.f     (column w: second coordinate)
+ *   pz is never read.  Coordinates outside (-1, 1) are legal (their terms
+ *   underflow).  For 0 <= h < grid_h, 0 <= w < grid_w:
+ *     sil[b,h,w] = sum_n ex[n,h] * ey[n,w],
+ *     ex[n,h] = exp(-(gx_n - h)^2 / (2 sigma_sq)), ey[n,w] likewise with gy_n, w
+ *   (grid_h + grid_w exponentials per point, each one hardware exp2 of
+ *   (d * d) * fl(-log2(e) / (2 sigma_sq)); products that would be denormal
+ *   may be flushed to zero).
+ *   Summation order of every cell: with the points in chunks of 128, eight
+ *   sequential partial sums -- partial k takes points 128 c + 16 k + j,
+ *   c ascending, then j = 0..15 ascending, each term added by one fused
+ *   multiply-add -- and then ((p0 + p1) + p2) + .. + p7.  It depends on n
+ *   alone: deterministic run to run, no float atomics, and cloud i evaluated
+ *   alone (b = 1) equals cloud i of any batch bit for bit.
+ *   Non-finite inputs, as the reference's sum: a NaN px or py makes every cell
+ *   of that cloud NaN; +-inf px or py contributes 0; pz changes nothing.
+ *   Every element of sil [b, grid_h, grid_w] is written.
+ * pcm_silhouette_backward: with G = grad_sil [b, grid_h, grid_w] (dL/dsil),
+ *     gradxyz[b,n,0] = (grid_h / 2) sum_h (-(gx_n - h) / sigma_sq) ex[n,h] (sum_w G[b,h,w] ey[n,w])
+ *     gradxyz[b,n,1] = (grid_w / 2) sum_w (-(gy_n - w) / sigma_sq) ey[n,w] (sum_h G[b,h,w] ex[n,h])
+ *     gradxyz[b,n,2] = 0 exactly
+ *   (autograd's backward of the sum above).  Order: per row h the columns in
+ *   slices of eight (pairwise inside a slice), rows ascending, then the slices
+ *   ascending; it depends on the grid alone.  Fully overwritten, no atomics.
+ *   Its result for non-finite coordinates is unspecified.
+ * layout: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, as
+ *   pcm_chamfer_forward_layout: read in place, and gradxyz is written in the
+ *   same layout.  perspective_transform returns such a view of planes
+ *   (projection.py:146), and that is what cont_proj receives.
+ * Validation, before any device call: b < 0, n < 0, a layout outside {0, 1},
+ *   grid_h < 1 or grid_w < 1, sigma_sq not finite or <= 0 ->
+ *   PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK); n == 0 or a null
+ *   pointer with b > 0 -> PCM_ERR_INVALID_ARG; grid_h or grid_w above
+ *   PCM_SILHOUETTE_MAX_GRID -> PCM_ERR_UNSUPPORTED.
+ */
+int pcm_silhouette_forward(const float *xyz, int b, int n, int layout, int grid_h, int grid_w,
+                           float sigma_sq, float *sil /* [b,grid_h,grid_w] */, void *stream);
+int pcm_silhouette_backward(const float *xyz, int b, int n, int layout, int grid_h, int grid_w,
+                            float sigma_sq, const float *grad_sil, float *gradxyz /* xyz's layout */, void *stream);
+
+/*
+ * Projection loss 'bce_prob' (extension): loss/proj_loss.py:17-19 and the mean
+ * of :43 -- six elementwise torch kernels and a reduction in the reference --
+ * with the gradient for pred from the same launch.  pred, gt, grad_pred hold
+ * `count` contiguous float32 elements.  Per element, in float32 and in this order:
+ *     a = pred + 1e-8f
+ *     c = fabsf((1.f - pred) - 1e-8f)
+ *     term = ((-gt) * logf(a)) * w - (1.f - gt) * logf(c)
+ *   loss_out[0] = sum(term) / (float)count                       (device float)
+ *   grad_pred[i] (nullable) = (-gt w / a + (1 - gt) / ((1.f - pred) - 1e-8f)) / (float)count,
+ *     the gradient of that mean with respect to pred; the two quotients can
+ *     cancel, so they are formed and added in double and rounded once.
+ * Summation order: workgroup k owns elements [2048 k, 2048 k + 2048); thread t
+ *   of 256 adds elements t, t + 256, .., t + 1792 in order (chain 8); a wave's
+ *   64 sums are added by six DPP steps (shift by 1, 2, 4, 8 lanes, then rows
+ *   16 and 32: chain 6); the four waves in ascending order (4).  A single
+ *   workgroup (count <= 2048) divides and stores.  Otherwise its partial goes
+ *   to the workspace and a second launch of one workgroup adds them: thread t
+ *   adds partials t, t + 256, .. in order (chain ceil(blocks / 256), 2 at
+ *   count = 2^20), then wave and workgroup as before (6 + 4).  Longest chain:
+ *   L = 18 + ceil(ceil(count / 2048) / 256) + 10 = PCM_PROJ_BCE_CHAIN for
+ *   2^19 < count <= 2^20, less below.  Deterministic, no float atomics.
+ * The workspace (pcm_proj_bce_workspace_bytes(count) bytes, at least 128 for
+ *   count > 0) needs no initialisation and holds no state between calls.
+ * Validation, before any device call: count < 0 -> PCM_ERR_INVALID_ARG;
+ *   count == 0 is a no-op (PCM_OK); a null pred / gt / loss_out ->
+ *   PCM_ERR_INVALID_ARG; a workspace that is NULL or too short ->
+ *   PCM_ERR_WORKSPACE.
+ */
+size_t pcm_proj_bce_workspace_bytes(long long count);
+int pcm_proj_bce(const float *pred, const float *gt, long long count, float w, float *loss_out,
+                 float *grad_pred /* nullable */, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
