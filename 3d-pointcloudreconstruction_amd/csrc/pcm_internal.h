@@ -56,6 +56,12 @@ int pcm_tune_chamfer_backward_f16(int variant, const uint16_t *xyz1, const uint1
                                   const float *graddist1, const float *graddist2, const int32_t *idx1,
                                   const int32_t *idx2, uint16_t *gradxyz1, uint16_t *gradxyz2, void *stream);
 int pcm_tune_emd_timeouts(const void *workspace, size_t workspace_bytes, int b, int n, void *stream);
+// pcm_fps with the workgroup size forced (64, 256 or 1024 threads; csrc/sampling.hip):
+// PCM_ERR_UNSUPPORTED when n exceeds what that size holds in registers (64 points a lane
+// at 64 and 256 threads); pcm_tune_fps_default_threads: the size pcm_fps picks for n
+int pcm_tune_fps(int threads, const float *xyz, int b, int n, int layout, int npoint, int start, int64_t *idx_out,
+                 float *sampled_out, void *stream);
+int pcm_tune_fps_default_threads(int n);
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ EXPORTED = (
     "pcm_chamfer_loss_grad_steps",
     "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
     "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
+    "pcm_fps",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -186,6 +187,13 @@ def _open(path):
         L.pcm_proj_bce_workspace_bytes.argtypes = [ctypes.c_longlong]
         L.pcm_proj_bce.restype = ci
         L.pcm_proj_bce.argtypes = [vp, vp, ctypes.c_longlong, cf, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_fps"):  # absent from A/B builds of older sources
+        L.pcm_fps.restype = ci
+        L.pcm_fps.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.pcm_tune_fps.restype = ci
+        L.pcm_tune_fps.argtypes = [ci, vp, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.pcm_tune_fps_default_threads.restype = ci
+        L.pcm_tune_fps_default_threads.argtypes = [ci]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -907,6 +915,45 @@ def proj_bce(pred, gt, w, loss_out, grad_pred=None, workspace=None) -> None:
             workspace = proj_bce_workspace(dev, count)
         _check(load_library().pcm_proj_bce(_ptr(pred), _ptr(gt), count, float(w), _ptr(loss_out), _ptr(grad_pred),
                                            _ptr(workspace), workspace.numel(), _stream(dev)), "pcm_proj_bce")
+
+
+FPS_MAX_POINTS = 16384  # include/pcm.h PCM_FPS_MAX_POINTS
+FPS_THREADS = (64, 256, 1024)  # workgroup sizes of csrc/sampling.hip
+
+
+def fps_default_threads(n: int) -> int:
+    """The workgroup size pcm_fps picks for clouds of n points (csrc/sampling.hip)."""
+    return int(load_library().pcm_tune_fps_default_threads(int(n)))
+
+
+def fps(xyz, layout, npoint, start, idx_out, sampled_out=None, threads=None) -> None:
+    """pcm_fps: idx_out [B, npoint] int64 (contiguous) = the farthest point
+    samples of the float32 cloud xyz [B, N, 3], given as rows (layout 0) or as
+    a view of channel planes (1, see cloud_layout), every cloud starting at
+    index `start`; sampled_out (optional, contiguous float32 [B, npoint, 3])
+    receives the sampled points from the same launch.  threads: internal
+    (tests, tools/bench_fps.py) -- force the workgroup size, one of FPS_THREADS."""
+    tensors = (xyz, idx_out) + (() if sampled_out is None else (sampled_out,))
+    dev = _require_device(*tensors)
+    if xyz.dtype != torch.float32:
+        raise TypeError(f"fps takes float32 clouds (got {xyz.dtype})")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError("fps takes clouds [B, N, 3]")
+    if cloud_layout(xyz) != int(layout):
+        raise ValueError("the cloud is not in the layout given (pcm_hip.cloud_layout)")
+    b, n = xyz.shape[0], xyz.shape[1]
+    npoint, start = int(npoint), int(start)
+    if tuple(idx_out.shape) != (b, npoint) or idx_out.dtype != torch.int64 or not idx_out.is_contiguous():
+        raise ValueError(f"idx_out must be contiguous int64 of shape {(b, npoint)}")
+    if sampled_out is not None and (tuple(sampled_out.shape) != (b, npoint, 3) or sampled_out.dtype != torch.float32
+                                    or not sampled_out.is_contiguous()):
+        raise ValueError(f"sampled_out must be contiguous float32 of shape {(b, npoint, 3)}")
+    with torch.cuda.device(dev):
+        tail = (_ptr(xyz), b, n, int(layout), npoint, start, _ptr(idx_out), _ptr(sampled_out), _stream(dev))
+        if threads is None:
+            _check(load_library().pcm_fps(*tail), "pcm_fps")
+        else:
+            _check(load_library().pcm_tune_fps(int(threads), *tail), "pcm_tune_fps")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

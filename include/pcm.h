@@ -20,6 +20,8 @@
  *                         <- cont_proj (utils/projection.py:4-67) and the 'bce_prob'
  *                            loss (loss/proj_loss.py:17-19, :43): torch ops in the
  *                            reference, finetune.py:154-162
+ *   pcm_fps               <- farthest_point_sample + index_points (utils/utils.py:316-360;
+ *                            a torch loop in the reference, utils/datasets_sample_pcl.py:87-94)
  *
  * Conventions:
  *   - all pointers are DEVICE pointers to contiguous row-major arrays:
@@ -393,6 +395,53 @@ int pcm_silhouette_backward(const float *xyz, int b, int n, int layout, int grid
 size_t pcm_proj_bce_workspace_bytes(long long count);
 int pcm_proj_bce(const float *pred, const float *gt, long long count, float w, float *loss_out,
                  float *grad_pred /* nullable */, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* Farthest point sampling (utils/datasets_sample_pcl.py:87-94)            */
+/* ---------------------------------------------------------------------- */
+
+/* Largest cloud (points per batch element) pcm_fps takes (else PCM_ERR_UNSUPPORTED). */
+#define PCM_FPS_MAX_POINTS 16384
+
+/*
+ * Farthest point sampling (extension): farthest_point_sample and index_points
+ * of utils/utils.py:316-360 -- npoint dependent iterations of 21 small device
+ * kernels each (torch.profiler's count), with a boolean-mask assignment that synchronises with the host
+ * -- as ONE launch of one workgroup per cloud, the running minima in registers.
+ *
+ * Contract.  Per cloud p[0..n), with far = start and run[k] = 1e10f for every
+ * k, repeat for i = 0 .. npoint - 1:
+ *     idx_out[b,i] = far
+ *     for every k:  d = fmaf(dz,dz,fmaf(dy,dy,dx*dx)), (dx,dy,dz) = p[k] - p[far]
+ *                   (the library's pinned order, as pcm_chamfer_forward);
+ *                   run[k] = d only if d < run[k]
+ *                   (a NaN distance never changes a running minimum)
+ *     far = the lowest k that attains max_k run[k]
+ *   Consequences: running minima are never NaN and every index is in [0, n)
+ *   for any input bits; npoint > n is legal and follows the same rule (once
+ *   every point of a cloud of distinct finite points is taken, index 0
+ *   repeats); a point with a NaN coordinate keeps run = 1e10f and, once it is
+ *   the lowest such point, repeats for the rest of the call.
+ *   The reference forms d as a torch sum of three squares; where its winner
+ *   beats the runner-up by more than a few float32 ulps, or ties it exactly,
+ *   the indices are the same.
+ *   sampled_out (nullable) [b, npoint, 3], always contiguous rows: p[idx_out[b,i]]
+ *   bit for bit, from the same launch.  idx_out [b, npoint] int64, as the
+ *   reference's torch.long centroids.  Every element of both is written.
+ * layout: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, read in place as
+ *   pcm_chamfer_forward_layout does.  start: the first index of every cloud
+ *   (the reference draws it from torch.randint(0, 1) or (1, 2): 0 or 1).
+ * No workspace, no allocation, no host synchronisation: one launch on `stream`,
+ *   capturable.  Deterministic; b is limited only by the grid.
+ * Validation, before any device call: b < 0, n < 0, npoint < 0 or a layout
+ *   outside {0, 1} -> PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK, also
+ *   with null pointers); n == 0 or npoint == 0, start < 0 or start >= n, a null
+ *   xyz or idx_out -> PCM_ERR_INVALID_ARG; n above PCM_FPS_MAX_POINTS ->
+ *   PCM_ERR_UNSUPPORTED.
+ */
+int pcm_fps(const float *xyz, int b, int n, int layout, int npoint, int start,
+            int64_t *idx_out /* [b, npoint] */, float *sampled_out /* [b, npoint, 3] or NULL */,
+            void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
