@@ -62,6 +62,13 @@ int pcm_tune_emd_timeouts(const void *workspace, size_t workspace_bytes, int b, 
 int pcm_tune_fps(int threads, const float *xyz, int b, int n, int layout, int npoint, int start, int64_t *idx_out,
                  float *sampled_out, void *stream);
 int pcm_tune_fps_default_threads(int n);
+// pcm_knn with the kernel form forced (csrc/knn.hip): 0 = what pcm_knn runs, 1 = one wave per 64
+// queries that ballots and inserts at once (libpcm_hip_tune.so only; elsewhere PCM_ERR_UNSUPPORTED), 2 = one wave with per-lane LDS queues drained together,
+// 3 = the queued form with the reference cloud split over four waves and their lists merged; the
+// same outputs bit for bit.  pcm_tune_knn_default_split: the waves per 64 queries pcm_knn picks
+int pcm_tune_knn(int variant, const float *query, const float *ref, int b, int n, int m, int layout_q, int layout_r,
+                 int k, float *dist_out, int32_t *idx_out, void *stream);
+int pcm_tune_knn_default_split(int b, int n);
 #ifdef __cplusplus
 }
 #endif

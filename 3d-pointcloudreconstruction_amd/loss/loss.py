@@ -2,7 +2,8 @@
 
 Same class and method names/signatures (loss/loss.py:12-37): ``Loss`` with
 ``get_emd_loss(pred, gt, radius=1.0)`` and ``get_chamfer_loss(pred, gt)``, so
-train.py:162-171 calls it unchanged.  Fixes the reference's module-scope
+train.py:162-171 calls it unchanged, plus ``get_repulsion_loss(pcd, h)``, which
+the reference dropped.  Fixes the reference's module-scope
 ``torch`` NameError (loss/loss.py:25 vs :40) and
 resolves the metric modules relative to this file instead of the working
 directory (loss/loss.py:1-7).
@@ -23,6 +24,10 @@ for _p in (os.path.join(_METRIC, "emd"), os.path.join(_METRIC, "chamfer3D")):
         sys.path.append(_p)
 from dist_chamfer_3D import chamfer_3DDist, chamfer_3DLoss  # noqa: E402,F401
 import emd_module as emd_func  # noqa: E402
+_HERE = os.path.dirname(os.path.abspath(__file__))
+if _HERE not in sys.path:
+    sys.path.append(_HERE)
+from repulsion_loss import repulsion_lossFunction  # noqa: E402
 
 
 class Loss(nn.Module):
@@ -43,6 +48,23 @@ class Loss(nn.Module):
         of <= 1024 points (chamfer_3DLoss); otherwise the reference sequence
         chamfer_3DDist + two torch.mean."""
         return chamfer_3DLoss()(pred, gt)
+
+    def get_repulsion_loss(self, pcd, h=0.0005):
+        """pcd is B x N x 3 (N >= 5): the mean over every point and its four
+        nearest other list slots of max(0, h - squared distance) -- PU-GAN's
+        repulsion term, one pcm_repulsion_loss call (loss/repulsion_loss.py).
+
+        The gradient is written in the input's layout, so the generator's
+        ``fake.transpose(2, 1)`` needs no copy in either direction.  An empty
+        batch (B = 0) returns NaN, as ``torch.mean`` of nothing does.
+
+        Differences from the reference's dropped method:
+          * the squared distances of a k=5 search are used directly, where the
+            reference squared the rounded square roots a k=20 search returned
+            and kept columns 1:5;
+          * this loss is differentiable; the reference's search ran under
+            ``torch.no_grad()``, so its loss could train nothing."""
+        return repulsion_lossFunction.apply(pcd, float(h))
 
 
 if __name__ == "__main__":

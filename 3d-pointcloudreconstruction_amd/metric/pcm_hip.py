@@ -40,6 +40,7 @@ EXPORTED = (
     "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
     "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
     "pcm_fps",
+    "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -194,6 +195,17 @@ def _open(path):
         L.pcm_tune_fps.argtypes = [ci, vp, ci, ci, ci, ci, ci, vp, vp, vp]
         L.pcm_tune_fps_default_threads.restype = ci
         L.pcm_tune_fps_default_threads.argtypes = [ci]
+    if hasattr(L, "pcm_knn"):  # absent from A/B builds of older sources
+        L.pcm_knn.restype = ci
+        L.pcm_knn.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.pcm_tune_knn.restype = ci
+        L.pcm_tune_knn.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+        L.pcm_tune_knn_default_split.restype = ci
+        L.pcm_tune_knn_default_split.argtypes = [ci, ci]
+        L.pcm_repulsion_workspace_bytes.restype = cs
+        L.pcm_repulsion_workspace_bytes.argtypes = [ci, ci]
+        L.pcm_repulsion_loss.restype = ci
+        L.pcm_repulsion_loss.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -954,6 +966,91 @@ def fps(xyz, layout, npoint, start, idx_out, sampled_out=None, threads=None) -> 
             _check(load_library().pcm_fps(*tail), "pcm_fps")
         else:
             _check(load_library().pcm_tune_fps(int(threads), *tail), "pcm_tune_fps")
+
+
+KNN_MAX_K = 32  # include/pcm.h PCM_KNN_MAX_K
+KNN_MAX_POINTS = 16384  # include/pcm.h PCM_KNN_MAX_POINTS
+KNN_WIDTHS = (4, 8, 16, 20, 32)  # list widths of csrc/knn.hip: k takes the first at or above it
+KNN_TILE = 1024  # reference points per LDS tile of csrc/knn.hip (kKnnTile)
+KNN_QUERIES = 64  # queries per workgroup of csrc/knn.hip
+KNN_SPLIT = 4  # waves the reference cloud is split over when the grid is small (kKnnSplit)
+KNN_VARIANTS = (0, 1, 2, 3)  # pcm_tune_knn: default, insert at once (libpcm_hip_tune.so), queued one wave, queued KNN_SPLIT waves
+REPULSION_K = 5  # slot 0 and the four slots pcm_repulsion_loss reads
+REPULSION_POINTS = 64  # points per workgroup of the repulsion kernel (kRepPoints)
+
+
+def knn_default_split(b: int, n: int) -> int:
+    """Waves per 64 queries pcm_knn picks for b clouds of n queries (csrc/knn.hip): KNN_SPLIT or 1."""
+    return int(load_library().pcm_tune_knn_default_split(int(b), int(n)))
+
+
+def _knn_cloud(t, layout, what):
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what} takes float32 clouds (got {t.dtype})")
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"{what} takes clouds [B, N, 3]")
+    if cloud_layout(t) != int(layout):
+        raise ValueError("the cloud is not in the layout given (pcm_hip.cloud_layout)")
+
+
+def knn(query, lay_q, ref, lay_r, k, dist, idx, variant=None) -> None:
+    """pcm_knn: dist [B, N, k] float32 (squared) and idx [B, N, k] int32, both
+    contiguous = for every point of the float32 cloud query [B, N, 3] its k
+    nearest points of ref [B, M, 3] in ascending (distance, index) order, empty
+    slots (+inf, -1); each cloud given as rows (layout 0) or as a view of
+    channel planes (1, see cloud_layout).  variant: internal (tests,
+    tools/bench_knn.py) -- force a kernel form, one of KNN_VARIANTS (pcm_tune_knn)."""
+    dev = _require_device(query, ref, dist, idx)
+    _knn_cloud(query, lay_q, "knn")
+    _knn_cloud(ref, lay_r, "knn")
+    b, n, m, k = query.shape[0], query.shape[1], ref.shape[1], int(k)
+    if ref.shape[0] != b:
+        raise ValueError("knn takes clouds of one batch size")
+    for t, dtype in ((dist, torch.float32), (idx, torch.int32)):
+        if tuple(t.shape) != (b, n, k) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"knn output must be contiguous {dtype} of shape {(b, n, k)}")
+    with torch.cuda.device(dev):
+        tail = (_ptr(query), _ptr(ref), b, n, m, int(lay_q), int(lay_r), k, _ptr(dist), _ptr(idx), _stream(dev))
+        if variant is None:
+            _check(load_library().pcm_knn(*tail), "pcm_knn")
+        else:  # the insert-at-once form is compiled into the tuning build only
+            L = load_tune_library() if int(variant) == 1 else load_library()
+            _check(L.pcm_tune_knn(int(variant), *tail), "pcm_tune_knn")
+
+
+def repulsion_workspace(dev: torch.device, b: int, n: int) -> torch.Tensor:
+    """Scratch for repulsion_loss (the k = 5 lists and the workgroups' partial
+    sums): ONE buffer per (device, current stream), grown when a larger problem
+    needs more; its content on entry is irrelevant and it holds nothing between calls."""
+    need = max(int(load_library().pcm_repulsion_workspace_bytes(b, n)), 8)
+    key = ("repulsion", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def repulsion_loss(xyz, lay, h, loss_out, gradxyz=None, workspace=None) -> None:
+    """pcm_repulsion_loss: loss_out[0] = mean over the points of the float32
+    cloud xyz [B, N, 3] (rows, or a view of channel planes: lay 1) and their
+    nearest four other list slots of max(0, h - squared distance) and, when
+    given, gradxyz (xyz's shape and layout) = its full gradient."""
+    tensors = (xyz, loss_out) + (() if gradxyz is None else (gradxyz,))
+    dev = _require_device(*tensors)
+    _knn_cloud(xyz, lay, "repulsion_loss")
+    if loss_out.dtype != torch.float32 or loss_out.numel() < 1:
+        raise ValueError("loss_out needs one float32")
+    if gradxyz is not None and (gradxyz.dtype != torch.float32 or gradxyz.shape != xyz.shape
+                                or cloud_layout(gradxyz) != int(lay)):
+        raise ValueError("gradxyz must have the cloud's dtype, shape and layout")
+    b, n = xyz.shape[0], xyz.shape[1]
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = repulsion_workspace(dev, b, n)
+        _check(load_library().pcm_repulsion_loss(_ptr(xyz), b, n, int(lay), float(h), _ptr(loss_out), _ptr(gradxyz),
+                                                 _ptr(workspace), workspace.numel(), _stream(dev)),
+               "pcm_repulsion_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

@@ -22,6 +22,9 @@
  *                            reference, finetune.py:154-162
  *   pcm_fps               <- farthest_point_sample + index_points (utils/utils.py:316-360;
  *                            a torch loop in the reference, utils/datasets_sample_pcl.py:87-94)
+ *   pcm_knn, pcm_repulsion_loss
+ *                         <- knn_cuda.KNN and Loss.get_repulsion_loss, which the reference's
+ *                            loss class was written around and then dropped (loss/loss.py:16-17)
  *
  * Conventions:
  *   - all pointers are DEVICE pointers to contiguous row-major arrays:
@@ -442,6 +445,87 @@ int pcm_proj_bce(const float *pred, const float *gt, long long count, float w, f
 int pcm_fps(const float *xyz, int b, int n, int layout, int npoint, int start,
             int64_t *idx_out /* [b, npoint] */, float *sampled_out /* [b, npoint, 3] or NULL */,
             void *stream);
+
+/* ---------------------------------------------------------------------- */
+/* k nearest neighbours and the repulsion loss                             */
+/* ---------------------------------------------------------------------- */
+
+/* Longest list pcm_knn returns (else PCM_ERR_UNSUPPORTED). */
+#define PCM_KNN_MAX_K 32
+/* Largest cloud (points per batch element), query or reference, that pcm_knn
+ * and pcm_repulsion_loss take (else PCM_ERR_UNSUPPORTED). */
+#define PCM_KNN_MAX_POINTS 16384
+
+/*
+ * k nearest neighbours (extension): the knn_cuda.KNN the reference's loss class
+ * was written around (the commented-out KNN(k=2) / KNN(k=20) members of
+ * loss/loss.py:16-17) as ONE launch, every query's list kept in registers.
+ *
+ * Contract.  For cloud bi and query i, candidate j (0 <= j < m) has
+ *     d = fmaf(dz,dz,fmaf(dy,dy,dx*dx)), (dx,dy,dz) = ref[bi,j] - query[bi,i]
+ *   (the library's pinned order, as pcm_chamfer_forward).
+ *   dist_out[bi,i,0..k) / idx_out[bi,i,0..k) are the k smallest pairs (d, j) in
+ *   lexicographic order -- d compared with '<', equal d broken by the lower j
+ *   -- in ascending slots; slot 0 is therefore exactly dist1 / idx1 of
+ *   pcm_chamfer_forward on finite clouds.
+ *   A candidate whose d is NaN or +inf is never listed.  Slots left without a
+ *   candidate hold (+inf, -1): when m < k, when candidates are non-finite, or
+ *   when the query is.  Nothing is excluded: in a self search (the same
+ *   pointer passed twice) a point lists itself.
+ *   Every element of both outputs is written; distances are SQUARED.
+ * layout_q / layout_r: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, each
+ *   cloud read in place as pcm_chamfer_forward_layout does.
+ * No workspace, no allocation, no host synchronisation, no atomics and no
+ *   waiting between workgroups: one launch on `stream`, capturable.
+ *   Deterministic; b is limited only by the grid.
+ * Validation, before any device call: negative sizes, a layout outside {0, 1}
+ *   or k < 1 -> PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK, also with
+ *   null pointers); n == 0, m == 0 or a null pointer -> PCM_ERR_INVALID_ARG;
+ *   k above PCM_KNN_MAX_K, or n or m above PCM_KNN_MAX_POINTS ->
+ *   PCM_ERR_UNSUPPORTED: nothing is launched and the outputs are left alone.
+ */
+int pcm_knn(const float *query, const float *ref, int b, int n, int m, int layout_q, int layout_r, int k,
+            float *dist_out /* [b, n, k] */, int32_t *idx_out /* [b, n, k] */, void *stream);
+
+/*
+ * Repulsion loss (extension): PU-GAN's point-distribution regulariser, the
+ * get_repulsion_loss the reference's loss class once had, with its gradient
+ * from the same call (the reference's ran knn_cuda under torch.no_grad() and
+ * could train nothing).
+ *
+ * Contract.  With (d[i,t], j[i,t]) slot t of point i's pcm_knn list (k = 5) in
+ * its own cloud, searched against itself:
+ *     loss_out[0] = (1 / (4 b n)) sum_bi sum_i sum_{t=1..4} max(0, h - d[i,t])
+ *   Slot 0 is skipped whatever it holds (the reference's dist[:, :, 1:5]); a
+ *   +inf slot contributes 0.  Each term h - d is formed in float32; the terms
+ *   are added in double in a fixed order (a point's four slots ascending, the
+ *   six DPP steps of a wave of 64 points, the waves' partials ascending in
+ *   strides of 64, then the six DPP steps again),
+ *   scaled by 1 / (4 b n) in double and rounded once.
+ *   gradxyz (nullable; xyz's shape AND layout): the full gradient.  Every
+ *   active term (h - d > 0) at (i, j) adds -(2 / (4 b n)) (p_i - p_j) to point i
+ *   and +(2 / (4 b n)) (p_i - p_j) to point j, so a point collects from its own
+ *   list and from every list it appears in.  Per component it is
+ *   fl(2 / (4 b n)) * a, where a is a float32 sum of (p_other - p_i) in a
+ *   fixed order: four partial sums, partial w over the points s with
+ *   (s mod 1024) div 256 == w whose active slots name the point, s ascending
+ *   (partial 0 begins with the point's own active slots 1..4, ascending),
+ *   then ((a0 + a1) + a2) + a3.  No float atomics: bit-identical from run to
+ *   run.  Fully overwritten.
+ * layout: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, read in place.
+ * Three launches on `stream`, capturable; no host synchronisation.  The
+ *   workspace (pcm_repulsion_workspace_bytes(b, n) bytes, 8-byte aligned)
+ *   holds the lists; it needs no initialisation and keeps no state.
+ * Validation, before any device call: b < 0, n < 0, a layout outside {0, 1} or
+ *   h not finite -> PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK;
+ *   loss_out is not written: the mean over nothing is the caller's to define);
+ *   n < 5, a null xyz or loss_out, a misaligned workspace ->
+ *   PCM_ERR_INVALID_ARG; n above PCM_KNN_MAX_POINTS -> PCM_ERR_UNSUPPORTED; a
+ *   workspace that is NULL or too short -> PCM_ERR_WORKSPACE.
+ */
+size_t pcm_repulsion_workspace_bytes(int b, int n);
+int pcm_repulsion_loss(const float *xyz, int b, int n, int layout, float h, float *loss_out /* 1 float */,
+                       float *gradxyz /* NULL, or xyz's layout */, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
