@@ -269,24 +269,6 @@ constexpr int kRepWaves = 4;      // waves that share them: each scans a quarter
 constexpr int kRepThreads = kRepPoints * kRepWaves;
 constexpr int kRepTile = 1024;    // source points per LDS tile: 4096 entries and the coordinates (28 KiB)
 
-template <int CTRL, int ROWMASK, bool BOUND>
-__device__ __forceinline__ double rep_dpp_add(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xf, BOUND);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xf, BOUND);
-    return x + __hiloint2double(hi, lo);
-}
-// the wave's sum in the order of pcm_wave_incl_scan's six DPP steps, returned wave-uniform
-__device__ __forceinline__ double rep_wave_sum(double x) {
-    x = rep_dpp_add<0x111, 0xf, true>(x);   // row_shr:1
-    x = rep_dpp_add<0x112, 0xf, true>(x);   // row_shr:2
-    x = rep_dpp_add<0x114, 0xf, true>(x);   // row_shr:4
-    x = rep_dpp_add<0x118, 0xf, true>(x);   // row_shr:8
-    x = rep_dpp_add<0x142, 0xa, false>(x);  // row_bcast:15 into rows 1, 3
-    x = rep_dpp_add<0x143, 0xc, false>(x);  // row_bcast:31 into rows 2, 3
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63),
-                            __builtin_amdgcn_readlane(__double2loint(x), 63));
-}
-
 // points blk * 64 + lane of cloud blockIdx.x / nblk: their four terms, the
 // workgroup's loss partial and (gradxyz non-null) their gradient.  Wave 0 adds
 // the points' own slots; every wave then scans its quarter of each tile's
@@ -331,7 +313,7 @@ __global__ __launch_bounds__(kRepThreads) void repulsion_kernel(const float *__r
                 }
             }
         }
-        const double wg = rep_wave_sum(terms);
+        const double wg = pcm_wave_sum_f64(terms);
         if (lane == 0) partial[blockIdx.x] = wg;
     }
     if (!gradxyz) return;
@@ -402,7 +384,7 @@ __global__ __launch_bounds__(64) void repulsion_finish_kernel(const double *__re
                                                               double inv_count, float *__restrict__ loss_out) {
     double acc = 0.0;
     for (int p = threadIdx.x; p < count; p += 64) acc += partial[p];
-    const double total = rep_wave_sum(acc);
+    const double total = pcm_wave_sum_f64(acc);
     if (threadIdx.x == 0) loss_out[0] = (float)(total * inv_count);
 }
 

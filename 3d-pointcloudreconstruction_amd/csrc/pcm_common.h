@@ -87,6 +87,25 @@ __device__ __forceinline__ int pcm_wave_incl_scan(int x) {
     return x;
 }
 
+// A double through one DPP step (two 32-bit moves; BOUND: shifted-in lanes read 0) added to the lane's own
+template <int CTRL, int ROWMASK, bool BOUND>
+__device__ __forceinline__ double pcm_dpp_add_f64(double x) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROWMASK, 0xf, BOUND);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROWMASK, 0xf, BOUND);
+    return x + __hiloint2double(hi, lo);
+}
+// the wave's sum in the order of pcm_wave_incl_scan's six DPP steps, returned wave-uniform
+__device__ __forceinline__ double pcm_wave_sum_f64(double x) {
+    x = pcm_dpp_add_f64<0x111, 0xf, true>(x);   // row_shr:1
+    x = pcm_dpp_add_f64<0x112, 0xf, true>(x);   // row_shr:2
+    x = pcm_dpp_add_f64<0x114, 0xf, true>(x);   // row_shr:4
+    x = pcm_dpp_add_f64<0x118, 0xf, true>(x);   // row_shr:8
+    x = pcm_dpp_add_f64<0x142, 0xa, false>(x);  // row_bcast:15 into rows 1, 3
+    x = pcm_dpp_add_f64<0x143, 0xc, false>(x);  // row_bcast:31 into rows 2, 3
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63),
+                            __builtin_amdgcn_readlane(__double2loint(x), 63));
+}
+
 // Workgroup-wide OR with ONE barrier, for a full workgroup in uniform control
 // flow.  HIP's __syncthreads_or re-reads the workgroup size from the dispatch
 // packet (an s_load that the next LDS wait also waits for) and takes three

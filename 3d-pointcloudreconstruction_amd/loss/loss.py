@@ -2,8 +2,8 @@
 
 Same class and method names/signatures (loss/loss.py:12-37): ``Loss`` with
 ``get_emd_loss(pred, gt, radius=1.0)`` and ``get_chamfer_loss(pred, gt)``, so
-train.py:162-171 calls it unchanged, plus ``get_repulsion_loss(pcd, h)``, which
-the reference dropped.  Fixes the reference's module-scope
+train.py:162-171 calls it unchanged, plus ``get_repulsion_loss(pcd, h)`` and
+``get_uniform_loss(pcd, percentage, radius)``, which the reference dropped.  Fixes the reference's module-scope
 ``torch`` NameError (loss/loss.py:25 vs :40) and
 resolves the metric modules relative to this file instead of the working
 directory (loss/loss.py:1-7).
@@ -12,6 +12,7 @@ EMD settings are the reference's training call (loss/loss.py:23: eps=0.05,
 iters=3000); they are keyword arguments here so the documented training
 setting (eps=0.005, iters=50, metric/emd/README.md:7) can be chosen.
 """
+import math
 import os
 import sys
 
@@ -28,6 +29,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 if _HERE not in sys.path:
     sys.path.append(_HERE)
 from repulsion_loss import repulsion_lossFunction  # noqa: E402
+from uniform_loss import uniform_lossFunction  # noqa: E402
+
+UNIFORM_MAX_NSAMPLE = 64  # pcm_hip.BALL_MAX_NSAMPLE: the longest group of one scale
 
 
 class Loss(nn.Module):
@@ -65,6 +69,58 @@ class Loss(nn.Module):
           * this loss is differentiable; the reference's search ran under
             ``torch.no_grad()``, so its loss could train nothing."""
         return repulsion_lossFunction.apply(pcd, float(h))
+
+    def get_uniform_loss(self, pcd, percentage=[0.004, 0.006, 0.008, 0.010, 0.012], radius=1.0):
+        """pcd is B x N x 3 (N >= 20): PU-GAN's uniform term as the reference's
+        dropped method had it, one pcm_uniform_loss call (loss/uniform_loss.py).
+        ``int(N * 0.05)`` farthest point seeds per cloud (started at point 0);
+        for every p of ``percentage`` a ball of radius sqrt(p * radius) around
+        each seed, cut to its first ``int(N * p)`` points in index order; the
+        mean distance m of a group member to its nearest other member;
+        (m - expect_len)^2 / (expect_len + 1e-8) averaged over the seeds, times
+        (p * 100)^2; the sum over p divided by ``len(percentage)``.
+
+        ``expect_len = sqrt(pi * radius^2 / N)`` is ported as the reference has
+        it.  PU-GAN's own formula differs: it is sqrt(2 * disk_area / 1.732)
+        with disk_area = pi * radius^2 * p / nsample, the spacing of a
+        hexagonal packing of each ball, one value per p.
+
+        Raises ValueError before any device call, naming the offending p, when
+        ``int(N * 0.05) < 1`` or some ``int(N * p)`` is below 2 or above 64
+        (groups of more than 64 points are out of scope: the defaults reach
+        N = 5333).  The gradient is written in the input's layout.  An empty
+        batch (B = 0) returns NaN.
+
+        Differences from the reference's dropped method:
+          * this loss is differentiable in the cloud; the reference's sampling,
+            grouping and search ran outside autograd;
+          * a slot whose nearest other member is at distance zero (a padding
+            copy, coincident points) carries no gradient;
+          * the ball query's padding rule (the first hit repeated, zeros
+            without a hit) is taken from pointnet2's source and is not verified
+            against pointnet2_ops, which is not installed here."""
+        if not isinstance(pcd, torch.Tensor) or pcd.dim() != 3:
+            raise ValueError("the uniform loss expects a cloud [B, N, 3]")
+        n = pcd.size(1)
+        percentage = [float(p) for p in percentage]
+        if not percentage:
+            raise ValueError("the uniform loss needs at least one percentage")
+        npoint = int(n * 0.05)
+        if npoint < 1:
+            raise ValueError(f"the uniform loss needs int(N * 0.05) >= 1 seeds (N = {n})")
+        nsample, ball_radius, weight = [], [], []
+        for p in percentage:
+            ns = int(n * p)
+            if ns < 2:
+                raise ValueError(f"percentage {p}: int(N * p) = {ns} points a group at N = {n}; at least 2 are needed")
+            if ns > UNIFORM_MAX_NSAMPLE:
+                raise ValueError(f"percentage {p}: int(N * p) = {ns} points a group at N = {n}; at most "
+                                 f"{UNIFORM_MAX_NSAMPLE} are supported")
+            nsample.append(ns)
+            ball_radius.append(math.sqrt(p * radius))
+            weight.append(math.pow(p * 100, 2) / len(percentage))
+        expect_len = math.sqrt(math.pi * (radius ** 2) / n)
+        return uniform_lossFunction.apply(pcd, npoint, nsample, ball_radius, weight, expect_len)
 
 
 if __name__ == "__main__":

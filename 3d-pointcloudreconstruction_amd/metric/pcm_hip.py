@@ -41,6 +41,7 @@ EXPORTED = (
     "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
     "pcm_fps",
     "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
+    "pcm_ball_query", "pcm_uniform_workspace_bytes", "pcm_uniform_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -206,6 +207,13 @@ def _open(path):
         L.pcm_repulsion_workspace_bytes.argtypes = [ci, ci]
         L.pcm_repulsion_loss.restype = ci
         L.pcm_repulsion_loss.argtypes = [vp, ci, ci, ci, cf, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_ball_query"):  # absent from A/B builds of older sources
+        L.pcm_ball_query.restype = ci
+        L.pcm_ball_query.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, ci, vp, vp, vp]
+        L.pcm_uniform_workspace_bytes.restype = cs
+        L.pcm_uniform_workspace_bytes.argtypes = [ci, ci, ci, ci, vp]
+        L.pcm_uniform_loss.restype = ci
+        L.pcm_uniform_loss.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, ctypes.c_double, vp, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1051,6 +1059,87 @@ def repulsion_loss(xyz, lay, h, loss_out, gradxyz=None, workspace=None) -> None:
         _check(load_library().pcm_repulsion_loss(_ptr(xyz), b, n, int(lay), float(h), _ptr(loss_out), _ptr(gradxyz),
                                                  _ptr(workspace), workspace.numel(), _stream(dev)),
                "pcm_repulsion_loss")
+
+
+BALL_MAX_NSAMPLE = 64  # include/pcm.h PCM_BALL_MAX_NSAMPLE
+UNIFORM_MAX_SCALES = 8  # include/pcm.h PCM_UNIFORM_MAX_SCALES
+BALL_TILE = 1024  # cloud points per LDS tile of csrc/grouping.hip (kBallTile)
+BALL_CENTRES = 4  # centres (waves) per workgroup of csrc/grouping.hip (kBallWaves)
+
+
+def ball_query(xyz, lay_x, new_xyz, lay_c, radius, nsample, idx, cnt=None) -> None:
+    """pcm_ball_query: idx [B, S, nsample] int32 (contiguous) = for every centre
+    of new_xyz [B, S, 3] the first nsample points of the float32 cloud xyz
+    [B, N, 3], in index order, whose pinned squared distance is below
+    fl(radius * radius), padded with the first hit (all 0 without one); cnt
+    (optional, [B, S] int32) = min(hits, nsample).  Each cloud is given as rows
+    (layout 0) or as a view of channel planes (1, see cloud_layout)."""
+    tensors = (xyz, new_xyz, idx) + (() if cnt is None else (cnt,))
+    dev = _require_device(*tensors)
+    _knn_cloud(xyz, lay_x, "ball_query")
+    _knn_cloud(new_xyz, lay_c, "ball_query")
+    b, n, s, nsample = xyz.shape[0], xyz.shape[1], new_xyz.shape[1], int(nsample)
+    if new_xyz.shape[0] != b:
+        raise ValueError("ball_query takes clouds of one batch size")
+    if tuple(idx.shape) != (b, s, nsample) or idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise ValueError(f"ball_query idx must be contiguous int32 of shape {(b, s, nsample)}")
+    if cnt is not None and (tuple(cnt.shape) != (b, s) or cnt.dtype != torch.int32 or not cnt.is_contiguous()):
+        raise ValueError(f"ball_query cnt must be contiguous int32 of shape {(b, s)}")
+    with torch.cuda.device(dev):
+        _check(load_library().pcm_ball_query(_ptr(xyz), _ptr(new_xyz), b, n, s, int(lay_x), int(lay_c), float(radius),
+                                             nsample, _ptr(idx), _ptr(cnt), _stream(dev)), "pcm_ball_query")
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def uniform_workspace(dev: torch.device, b: int, n: int, npoint: int, nsample) -> torch.Tensor:
+    """Scratch for uniform_loss (the seeds and one record per group slot): ONE
+    buffer per (device, current stream), grown when a larger problem needs more;
+    its content on entry is irrelevant and it holds nothing between calls."""
+    need = max(int(load_library().pcm_uniform_workspace_bytes(b, n, int(npoint), len(nsample), _int_array(nsample))),
+               8)
+    key = ("uniform", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def uniform_loss(xyz, lay, npoint, nsample, ball_radius, weight, expect_len, loss_out, gradxyz=None, groups=None,
+                 workspace=None) -> None:
+    """pcm_uniform_loss on the float32 cloud xyz [B, N, 3] (rows, or a view of
+    channel planes: lay 1): loss_out[0] = the uniform loss over npoint farthest
+    point seeds and the scales (nsample[q], ball_radius[q], weight[q]) -- host
+    sequences of one length -- around expect_len; when given, gradxyz (xyz's
+    shape and layout) = its full gradient and groups ([B, npoint, sum nsample]
+    int32, contiguous) = the seeds' index lists, scale after scale."""
+    tensors = (xyz, loss_out) + tuple(t for t in (gradxyz, groups) if t is not None)
+    dev = _require_device(*tensors)
+    _knn_cloud(xyz, lay, "uniform_loss")
+    if loss_out.dtype != torch.float32 or loss_out.numel() < 1:
+        raise ValueError("loss_out needs one float32")
+    if gradxyz is not None and (gradxyz.dtype != torch.float32 or gradxyz.shape != xyz.shape
+                                or cloud_layout(gradxyz) != int(lay)):
+        raise ValueError("gradxyz must have the cloud's dtype, shape and layout")
+    nsample = [int(v) for v in nsample]
+    if not (len(nsample) == len(ball_radius) == len(weight)):
+        raise ValueError("uniform_loss takes nsample, ball_radius and weight of one length")
+    b, n, npoint = xyz.shape[0], xyz.shape[1], int(npoint)
+    if groups is not None and (tuple(groups.shape) != (b, npoint, sum(nsample)) or groups.dtype != torch.int32
+                               or not groups.is_contiguous()):
+        raise ValueError(f"groups must be contiguous int32 of shape {(b, npoint, sum(nsample))}")
+    radii = (ctypes.c_float * len(nsample))(*[float(v) for v in ball_radius])
+    weights = (ctypes.c_double * len(nsample))(*[float(v) for v in weight])
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = uniform_workspace(dev, b, n, npoint, nsample)
+        _check(load_library().pcm_uniform_loss(_ptr(xyz), b, n, int(lay), npoint, len(nsample), _int_array(nsample),
+                                               radii, weights, float(expect_len), _ptr(loss_out), _ptr(gradxyz),
+                                               _ptr(groups), _ptr(workspace), workspace.numel(), _stream(dev)),
+               "pcm_uniform_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

@@ -528,6 +528,124 @@ int pcm_repulsion_loss(const float *xyz, int b, int n, int layout, float h, floa
                        float *gradxyz /* NULL, or xyz's layout */, void *workspace, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Ball query, grouping and the uniform loss                               */
+/* ---------------------------------------------------------------------- */
+
+/* Longest list pcm_ball_query returns, and longest group of one scale of
+ * pcm_uniform_loss (else PCM_ERR_UNSUPPORTED). */
+#define PCM_BALL_MAX_NSAMPLE 64
+/* Most scales (radii) one pcm_uniform_loss call takes. */
+#define PCM_UNIFORM_MAX_SCALES 8
+
+/*
+ * Ball query (extension): pointnet2's ball_query, which the reference's dropped
+ * get_uniform_loss called through pointnet2_ops, as ONE launch.
+ * pointnet2_ops is not installed where this library was written and could not
+ * be fetched: the rule below -- in particular the padding -- is pointnet2's
+ * published one, stated from its source; it is NOT verified against that
+ * library.  This text is the contract.
+ *
+ * Contract.  For cloud bi and centre c, point k (0 <= k < n) has
+ *     d = fmaf(dz,dz,fmaf(dy,dy,dx*dx)), (dx,dy,dz) = xyz[bi,k] - new_xyz[bi,c]
+ *   (the library's pinned order, as pcm_knn), and r2 = radius * radius, rounded
+ *   once to float32.  Point k is a hit iff d < r2: a NaN d is never a hit and a
+ *   point at exactly r2 is outside.  With h_0 < h_1 < ... the hits in ascending
+ *   k and c_n = min(number of hits, nsample):
+ *     idx_out[bi,c,t] = h_t for t < c_n;
+ *     every remaining slot holds h_0 (pointnet2's padding: the first hit
+ *       repeated); with no hit every slot holds 0 (its zero-initialised output);
+ *     cnt_out[bi,c] = c_n (cnt_out is nullable).
+ *   A group is the first nsample hits IN INDEX ORDER, not the nearest ones.
+ *   Every element of both outputs is written and every index is in [0, n) for
+ *   any input bits.
+ * layout_xyz / layout_new: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes,
+ *   each cloud read in place as pcm_knn does.
+ * No workspace, no allocation, no host synchronisation, no atomics and no
+ *   waiting between workgroups: one launch on `stream`, capturable.
+ *   Deterministic; b is limited only by the grid.
+ * Validation, before any device call: negative sizes, a layout outside {0, 1},
+ *   nsample < 1 or a radius that is not finite and positive ->
+ *   PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK, also with null
+ *   pointers); n == 0, s == 0 or a null xyz, new_xyz or idx_out ->
+ *   PCM_ERR_INVALID_ARG; nsample above PCM_BALL_MAX_NSAMPLE or n above
+ *   PCM_KNN_MAX_POINTS -> PCM_ERR_UNSUPPORTED: nothing is launched and the
+ *   outputs are left alone.
+ */
+int pcm_ball_query(const float *xyz, const float *new_xyz, int b, int n, int s, int layout_xyz, int layout_new,
+                   float radius, int nsample, int32_t *idx_out /* [b, s, nsample] */,
+                   int32_t *cnt_out /* [b, s] or NULL */, void *stream);
+
+/*
+ * Uniform loss (extension): PU-GAN's other point-distribution regulariser, the
+ * get_uniform_loss the reference's loss class once had, with its full gradient
+ * from the same call.  nsample, ball_radius and weight are HOST arrays of
+ * nscales entries, read before the call returns (they travel as kernel
+ * arguments).
+ *
+ * Contract.
+ *   Seeds: seed[bi, 0..npoint) are pcm_fps's indices of cloud bi with start = 0.
+ *   Groups: for scale q and seed s, G[0..nsample[q]) is pcm_ball_query's list
+ *   around p[seed] in the seed's own cloud with radius ball_radius[q] (the
+ *   same unverified padding rule).  groups_out (nullable) receives them:
+ *   row (bi, s) holds the lists of scale 0, 1, .. one after the other.
+ *   For slot t of a group: the pcm_knn distances (pinned order, p[G_v] - p[G_t])
+ *   to every slot v of the group, v = t included; the pairs (distance, v) in
+ *   lexicographic order; e_t is the distance of the second-smallest pair and
+ *   v* its slot -- exactly slot 1 of pcm_knn(k = 2) on the group, with its
+ *   rules that a NaN or +inf distance is never listed and an unfilled slot is
+ *   +inf.  root_t = sqrtf(e_t), correctly rounded; u_t = root_t + 1e-8f in
+ *   float32 (the reference's abs is then a no-op).  From here in double:
+ *     m = (sum_t u_t) / nsample[q];  term = (m - L)^2 / (L + 1e-8), L = expect_len;
+ *     loss_out[0] = sum_q weight[q] (sum_{bi,s} term) / (b npoint), rounded once.
+ *   Fixed order of the sums: a seed's slots are numbered (first slot of q) + t,
+ *   S = sum_q nsample[q] in all, and taken 64 at a time, lane = number mod 64; a
+ *   group's u_t among them are added by the six DPP steps of a wave (the other
+ *   lanes hold 0) and the passes' sums ascending;
+ *   a seed's weight[q] * term over q ascending; of the seeds'
+ *   sums, numbered bi * npoint + s, thread t of 1024 adds t, t + 1024, ..
+ *   ascending, every wave its 64 threads by the six DPP steps, and the sixteen
+ *   waves' sums are added ascending; the division by b npoint last.
+ *   gradxyz (nullable; xyz's shape AND layout), fully overwritten: seeds, ball
+ *   membership and the choice of neighbour carry no gradient.  With
+ *     c = weight[q] 2 (m - L) / ((L + 1e-8) b npoint nsample[q])   (double),
+ *   every slot t with 0 < e_t < inf contributes g = fl(c) * ((p_i - p_j) / root_t)
+ *   (float32 throughout) to point i = G_t and -g to point j = G_{v*}.  A slot
+ *   with e_t == 0 (a padding copy, coincident points) contributes nothing: the
+ *   subgradient, where the reference's would be infinite.  A point that fills
+ *   several slots collects from each.  No float atomics: the slots' records
+ *   (i, j, g) of a cloud are numbered r = (s * S + first slot of q + t) and a
+ *   point's gradient is a float32 sum of four partial
+ *   sums, partial w over the records r with (r mod 1024) div 256 == w that
+ *   name the point, r ascending, +g as point i before -g as point j, then
+ *   ((a0 + a1) + a2) + a3: bit-identical from run to run.
+ *   Non-finite input: the call returns and every index written is in range;
+ *   the loss follows IEEE from the rules above (it may be inf or NaN); the
+ *   gradient is then unspecified.
+ * layout: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, read in place.
+ * Four launches on `stream` (three without gradxyz), capturable; no host
+ *   synchronisation and no waiting between workgroups.  The workspace
+ *   (pcm_uniform_workspace_bytes bytes, 8-byte aligned) holds the seeds and
+ *   the records; it needs no initialisation and keeps no state.
+ * Validation, before any device call: b < 0, n < 0, a layout outside {0, 1},
+ *   nscales outside [1, PCM_UNIFORM_MAX_SCALES], a null host array,
+ *   npoint < 1, any nsample[q] < 2, a ball_radius, weight or expect_len that
+ *   is not finite, a ball_radius or expect_len that is not positive ->
+ *   PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK; loss_out is not
+ *   written); n == 0, a null xyz or loss_out, a misaligned workspace ->
+ *   PCM_ERR_INVALID_ARG; any nsample[q] above PCM_BALL_MAX_NSAMPLE or n above
+ *   PCM_KNN_MAX_POINTS -> PCM_ERR_UNSUPPORTED; a workspace that is NULL or too
+ *   short -> PCM_ERR_WORKSPACE.
+ * pcm_uniform_workspace_bytes: 0 when b, n or npoint is not positive or the
+ *   scales would be rejected as invalid arguments.
+ */
+size_t pcm_uniform_workspace_bytes(int b, int n, int npoint, int nscales, const int *nsample);
+int pcm_uniform_loss(const float *xyz, int b, int n, int layout, int npoint, int nscales, const int *nsample,
+                     const float *ball_radius, const double *weight, double expect_len,
+                     float *loss_out /* 1 float */, float *gradxyz /* NULL, or xyz's layout */,
+                     int32_t *groups_out /* NULL, or [b, npoint, sum_q nsample[q]] */, void *workspace,
+                     size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
 /* ---------------------------------------------------------------------- */
 
