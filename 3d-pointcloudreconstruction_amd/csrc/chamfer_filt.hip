@@ -787,13 +787,33 @@ __device__ __forceinline__ float filt_forward(const TIn *__restrict__ Q, const T
 // g = quarter, quarter + 4, ...  A chunk (the unit of the proof) is one
 // target group seen by one lane group: targets 64 g + 16 i + 4 (l>>4) + r,
 // i, r in 0..3 -- 16 candidates, rescanned in ascending order.
+//
+// Around the screen the forward is filt_forward's: no barrier before staging
+// (every wave loads the 256 queries and reduces the centre itself), the next
+// group's A tiles read a group ahead, the lane groups folded in registers,
+// the merge of the four quarters, the proof and the exact rescan in one pass
+// by (query, part) threads, near ties listed with a plan and rescanned by one
+// wave each over the planned chunks only, and the per-query bound: E above
+// with (R + |q'|)^2 replaced by min((R + |q'|)^2, (2|q'| + sqrt(d_b))^2), by
+// filt_forward's argument.  The one-launch step's default (fused variant 19).
 // ---------------------------------------------------------------------------
 constexpr float kFiltU80 = 4.76837158203125e-06f;  // 80 u = 80 * 2^-24
 constexpr int kMfmaQW = 256, kMfmaNT = 512, kMfmaTile = 1024;
+// Operand rows in LDS: 768 bytes per 16-row MFMA tile, K-slice-major inside
+// the tile -- 16 bytes (K 8j..8j+7, j = 0..2) of row 16 t + c at uint4 index
+// 48 t + 16 j + c -- so lane groups 0-2 read a tile as lane l's uint4 48 t + l
+// (consecutive bytes) and a wave's row store covers consecutive 256-byte runs
+// (row-major 64-byte rows put every fourth lane of a store on the same banks:
+// staging took 2.4 us that way, profiles/mfma_screen).  K 24..31 are zero in
+// every row of both operands: lane group 3 reads them from a zero region that
+// spans the four tile offsets of a group.  With the zero slices stored the
+// arena would exceed the gradient phase's 64 KiB and the grid's polling
+// workgroup would no longer be resident beside a CU's forward workgroup.
 struct MfmaLds {
-    static constexpr int kA = kMfmaTile * 64;                    // target rows, 32 bf16 each
-    static constexpr int kQB = kMfmaQW * 64;                     // query rows, 32 bf16 each
-    static constexpr int kScan = kA + kQB;
+    static constexpr int kA = kMfmaTile * 48;                    // target rows, K 0..23
+    static constexpr int kZ = (3 * 48 + 16) * 16;                // zeros: tile offsets 0, 48, 96, 144 (+ 16 columns)
+    static constexpr int kQB = kMfmaQW * 48;                     // query rows, K 0..23
+    static constexpr int kScan = kA + kZ + kQB;
     static constexpr int kTail = 3 * kMfmaTile * 4 + 3 * 4 * kMfmaQW * 4;  // raw tile + 4 partials
     static constexpr int kBytes = kScan > kTail ? kScan : kTail;
 };
@@ -825,118 +845,175 @@ __device__ __forceinline__ unsigned bf_pair(unsigned lo, unsigned hi) {
 // lanes -- one query each, chunks of stride-16 quads -- spread over the banks
 [[maybe_unused]] __device__ __forceinline__ int mslot(int p) { return (p & ~63) | ((p + 4 * ((p >> 6) & 7)) & 63); }
 
+// One halving step of the fold over a wave's four lane groups, which hold
+// partials (best, second, chunk) of the same queries.  Lanes l and l ^ 32
+// (k32; else l ^ 16) hold partials X of query A and Y of query B.
+// v_permlane32/16_swap exchanges X of the upper lane with Y of the lower one,
+// so the lower lane ends with both partials of A and the upper lane with both
+// of B: each folds the query it keeps into X, and the step halves the queries
+// a lane carries.  The fold is symmetric.  No LDS round trip.
+template <bool k32>
+__device__ __forceinline__ void mfma_fold_step(float &b, float &s, int &c, float bo, float so, int co) {
+    auto swap = [](unsigned &x, unsigned &y) {
+        if constexpr (k32) {
+            const auto r = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+            x = r[0];
+            y = r[1];
+        } else {
+            const auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+            x = r[0];
+            y = r[1];
+        }
+    };
+    unsigned b0 = __float_as_uint(b), b1 = __float_as_uint(bo), s0 = __float_as_uint(s), s1 = __float_as_uint(so);
+    unsigned c0 = (unsigned)c, c1 = (unsigned)co;
+    swap(b0, b1);
+    swap(s0, s1);
+    swap(c0, c1);
+    const float fb0 = __uint_as_float(b0), fb1 = __uint_as_float(b1);
+    const bool better = (fb1 < fb0) | ((fb1 == fb0) & ((int)c1 < (int)c0));
+    s = __builtin_fminf(__builtin_fminf(__uint_as_float(s0), __uint_as_float(s1)), better ? fb0 : fb1);
+    b = better ? fb1 : fb0;
+    c = better ? (int)c1 : (int)c0;
+}
+
+// Gr / tag: the argmin granules of the one-launch step's hand-off (as
+// filt_forward publishes them); kown: the thread's own argmin; LQ / LT: the
+// clouds' layouts (prologue loads only: everything after works on registers
+// and LDS).
 template <bool kSc1>
 __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, const float *__restrict__ T, int nq,
                                                    int nt, int qbase, float *__restrict__ D, int32_t *__restrict__ I,
-                                                   unsigned char *arena) {
-    constexpr int QW = kMfmaQW, NT = kMfmaNT, W = NT / 64, TILE = kMfmaTile;
+                                                   unsigned char *arena, unsigned long long *__restrict__ Gr = nullptr,
+                                                   unsigned long long tag = 0, PcmLay LQ = PcmLay{3, 1},
+                                                   PcmLay LT = PcmLay{3, 1}, int *kown = nullptr) {
+    constexpr int QW = kMfmaQW, NT = kMfmaNT, W = NT / 64, TILE = kMfmaTile, QPT = QW / 64;
     constexpr int kPer = TILE / NT;  // staged targets per thread
-    uint4 *sA = reinterpret_cast<uint4 *>(arena);                      // [TILE][4] x 16 B
-    uint4 *sQB = reinterpret_cast<uint4 *>(arena + MfmaLds::kA);        // [QW][4]
+    static_assert(NT == 2 * QW && QPT == 4, "thread = (query slot, part of 2); wave w holds query copy w mod 4");
+    uint4 *sA = reinterpret_cast<uint4 *>(arena);                                   // [TILE / 16][3][16] x 16 B
+    uint4 *sZ = reinterpret_cast<uint4 *>(arena + MfmaLds::kA);                     // zeros
+    uint4 *sQB = reinterpret_cast<uint4 *>(arena + MfmaLds::kA + MfmaLds::kZ);      // [QW / 16][3][16]
+    auto rowslot = [](int p, int j) { return 48 * (p >> 4) + 16 * j + (p & 15); };  // K slice j < 3 of row p
     float(*sT)[TILE] = reinterpret_cast<float(*)[TILE]>(arena);         // raw x, y, z (after the scan)
     float(*sPB)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4);
     float(*sPS)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4 + 4 * QW * 4);
     int(*sPC)[QW] = reinterpret_cast<int(*)[QW]>(arena + 3 * TILE * 4 + 8 * QW * 4);
-    __shared__ float sQx[QW], sQy[QW], sQz[QW];  // raw queries
-    __shared__ float sD[QW];
+    __shared__ float sD[QW];  // near-tie results
     __shared__ int sK[QW];
-    __shared__ int sFc[QW];
+    __shared__ unsigned sPlan[QW];
     __shared__ float sHD[2][QW];
     __shared__ int sHK[2][QW];
     __shared__ float sRmax[W];
-    __shared__ float sCen[4];
     __shared__ int sList[QW];
     __shared__ int sNList;
+    __shared__ int sNFm[W];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // ---- raw queries (thread s < QW owns query slot s) and the first tile
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    bool nonfinite = false;
-    if (tid < QW) {
-        const int qc = min(qbase + tid, nq - 1);
-        qx = pcm_ld(Q + 3 * (size_t)qc + 0);
-        qy = pcm_ld(Q + 3 * (size_t)qc + 1);
-        qz = pcm_ld(Q + 3 * (size_t)qc + 2);
+    // ---- queries (every wave holds the same QW queries: lane + 64 qq) and
+    // this thread's targets: unconditional clamped loads, all in flight at once
+    float rx[QPT], ry[QPT], rz[QPT];
+#pragma unroll
+    for (int qq = 0; qq < QPT; ++qq) {
+        const int qc = min(qbase + qq * 64 + lane, nq - 1);
+        rx[qq] = pcm_ld(Q + pcm_at(LQ, qc, 0));
+        ry[qq] = pcm_ld(Q + pcm_at(LQ, qc, 1));
+        rz[qq] = pcm_ld(Q + pcm_at(LQ, qc, 2));
     }
     float tv[kPer][3];
 #pragma unroll
     for (int r = 0; r < kPer; ++r) {
         const int p = min(tid + r * NT, nt - 1);
 #pragma unroll
-        for (int d = 0; d < 3; ++d) tv[r][d] = pcm_ld(T + 3 * (size_t)p + d);
+        for (int d = 0; d < 3; ++d) tv[r][d] = pcm_ld(T + pcm_at(LT, p, d));
     }
-    {
-        const bool live = tid < QW && qbase + tid < nq;
-        if (live) nonfinite |= !(pcm_finite(qx) && pcm_finite(qy) && pcm_finite(qz));
-        float cx = live ? qx : 0.f, cy = live ? qy : 0.f, cz = live ? qz : 0.f, cn = live ? 1.f : 0.f;
-        if (wave < QW / 64) {
-            cx = wave_sum(cx);
-            cy = wave_sum(cy);
-            cz = wave_sum(cz);
-            cn = wave_sum(cn);
-            if (lane == 0) { sRmax[wave] = cx; sHD[0][wave] = cy; sHD[1][wave] = cz; sD[wave] = cn; }
+    bool nonfinite = false;
+    float cx = 0.f, cy = 0.f, cz = 0.f;
+    int qcnt = 0;
+#pragma unroll
+    for (int qq = 0; qq < QPT; ++qq) {
+        if (qbase + qq * 64 + lane < nq) {
+            nonfinite |= !(pcm_finite(rx[qq]) && pcm_finite(ry[qq]) && pcm_finite(rz[qq]));
+            cx += rx[qq];
+            cy += ry[qq];
+            cz += rz[qq];
+            ++qcnt;
         }
-        if (tid < QW) { sQx[tid] = qx; sQy[tid] = qy; sQz[tid] = qz; }
-        if (tid == 0) sNList = 0;
-        __syncthreads();
-        if (tid == 0) {  // fixed order over the query waves
-            float sx = 0.f, sy = 0.f, sz = 0.f, sn = 0.f;
-            for (int w = 0; w < QW / 64; ++w) { sx += sRmax[w]; sy += sHD[0][w]; sz += sHD[1][w]; sn += sD[w]; }
-            sCen[0] = sx / sn;
-            sCen[1] = sy / sn;
-            sCen[2] = sz / sn;
-        }
-        __syncthreads();
     }
+    if (tid == 0) sNList = 0;  // first read after the staging barrier
+    // every wave reduces the centre itself (same instructions, same bits): no barrier
+    const float cn = (float)wave_sum_dpp(qcnt);
+    const float c0 = wave_sum_dpp(cx) / cn, c1 = wave_sum_dpp(cy) / cn, c2 = wave_sum_dpp(cz) / cn;
     PCM_STAMP(1);
 #ifdef PCM_STAMPS
     if (tid == 0 && blockIdx.x < 4096)  // shader-clock cycles beside the 100 MHz stamps (clock estimate)
         g_pcm_stamps[(8192 + blockIdx.x) * 8 + 1] = __builtin_amdgcn_s_memtime();
 #endif
-    const float c0 = sCen[0], c1 = sCen[1], c2 = sCen[2];
 
-    // ---- rows: queries (thread s < QW) and targets (kPer per thread), 16 dwords each
-    if (tid < QW) {
+    // ---- this thread's query: slot s = tid mod QW is register copy wave mod 4
+    // of its lane.  It splits that query's row (waves 0-3 store the row's first
+    // half, waves 4-7 the second) and later proves and rescans it as part
+    // tid / QW.
+    float qx = rx[0], qy = ry[0], qz = rz[0];
+#pragma unroll
+    for (int qq = 1; qq < QPT; ++qq)
+        if ((wave & (QPT - 1)) == qq) { qx = rx[qq]; qy = ry[qq]; qz = rz[qq]; }
+    const float qxc = qx - c0, qyc = qy - c1, qzc = qz - c2;
+    {
         unsigned H01, M01, L01, H2, M2, L2;
-        split3x2(qx - c0, qy - c1, H01, M01, L01);
-        split3x2(qz - c2, 0.f, H2, M2, L2);
+        split3x2(qxc, qyc, H01, M01, L01);
+        split3x2(qzc, 0.f, H2, M2, L2);
         // K 6d..6d+5: qh, qm, qh, ql, qh, qm; K 18..20: 1
         const unsigned one2 = 0x3f803f80u, one0 = 0x00003f80u;
-        sQB[4 * tid + 0] = make_uint4(bf_pair<0, 0>(H01, M01), bf_pair<0, 0>(H01, L01), bf_pair<0, 0>(H01, M01),
-                                      bf_pair<1, 1>(H01, M01));
-        sQB[4 * tid + 1] = make_uint4(bf_pair<1, 1>(H01, L01), bf_pair<1, 1>(H01, M01), bf_pair<0, 0>(H2, M2),
-                                      bf_pair<0, 0>(H2, L2));
-        sQB[4 * tid + 2] = make_uint4(bf_pair<0, 0>(H2, M2), one2, one0, 0u);
-        sQB[4 * tid + 3] = make_uint4(0u, 0u, 0u, 0u);
+        const int row = tid & (QW - 1);
+        if (wave < QPT) {
+            sQB[rowslot(row, 0)] = make_uint4(bf_pair<0, 0>(H01, M01), bf_pair<0, 0>(H01, L01), bf_pair<0, 0>(H01, M01),
+                                              bf_pair<1, 1>(H01, M01));
+            sQB[rowslot(row, 1)] = make_uint4(bf_pair<1, 1>(H01, L01), bf_pair<1, 1>(H01, M01), bf_pair<0, 0>(H2, M2),
+                                              bf_pair<0, 0>(H2, L2));
+        } else {
+            sQB[rowslot(row, 2)] = make_uint4(bf_pair<0, 0>(H2, M2), one2, one0, 0u);
+            if (row < MfmaLds::kZ / 16) sZ[row] = make_uint4(0u, 0u, 0u, 0u);
+        }
     }
-    const int ntp = (nt + 63) & ~63;  // whole 64-target groups; pad rows screen as +inf
+    // ---- target rows, 16 dwords each.  The loads were clamped, so a pad row
+    // (p >= nt, up to whole 64-target groups) holds a real point until the
+    // selects below make it screen as +inf; checking it again is harmless.
+    const int ntp = (nt + 63) & ~63;
     float rt2 = 0.f;
+    uint4 rows[kPer][3];
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) {
+        nonfinite |= !(pcm_finite(tv[r][0]) && pcm_finite(tv[r][1]) && pcm_finite(tv[r][2]));
+        const float x = tv[r][0] - c0, y = tv[r][1] - c1, z = tv[r][2] - c2;
+        const float w = __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
+        unsigned H01, M01, L01, H23, M23, L23;
+        split3x2(-2.f * x, -2.f * y, H01, M01, L01);
+        split3x2(-2.f * z, w, H23, M23, L23);
+        // (a w whose high part rounds up to +inf screens as NaN, which the min
+        // folds drop: its high part in R makes the bound infinite instead)
+        rt2 = __builtin_fmaxf(rt2, __builtin_fmaxf(w, bf_hi(H23)));
+        const bool pad = tid + r * NT >= nt;
+        // K 6d..6d+5: uh, uh, um, uh, ul, um; K 18..20: wh, wm, wl; pad: K 18 (wh) = +inf, the rest 0
+        rows[r][0] = make_uint4(bf_pair<0, 0>(H01, H01), bf_pair<0, 0>(M01, H01), bf_pair<0, 0>(L01, M01),
+                                bf_pair<1, 1>(H01, H01));
+        rows[r][1] = make_uint4(bf_pair<1, 1>(M01, H01), bf_pair<1, 1>(L01, M01), bf_pair<0, 0>(H23, H23),
+                                bf_pair<0, 0>(M23, H23));
+        rows[r][2] = make_uint4(bf_pair<0, 0>(L23, M23), bf_pair<1, 1>(H23, M23), L23 >> 16, 0u);
+        if (pad) {
+            rows[r][0] = make_uint4(0u, 0u, 0u, 0u);
+            rows[r][1] = make_uint4(0u, 0u, 0u, 0u);
+            rows[r][2] = make_uint4(0u, 0x00007f80u, 0u, 0u);
+        }
+    }
 #pragma unroll
     for (int r = 0; r < kPer; ++r) {
         const int p = tid + r * NT;
-        if (p < ntp) {
-            uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0, r2 = make_uint4(0u, 0x00007f80u, 0u, 0u);  // pad: K 18 (wh) = +inf
-            if (p < nt) {
-                nonfinite |= !(pcm_finite(tv[r][0]) && pcm_finite(tv[r][1]) && pcm_finite(tv[r][2]));
-                const float x = tv[r][0] - c0, y = tv[r][1] - c1, z = tv[r][2] - c2;
-                const float w = __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
-                rt2 = __builtin_fmaxf(rt2, w);
-                unsigned H01, M01, L01, H23, M23, L23;
-                split3x2(-2.f * x, -2.f * y, H01, M01, L01);
-                split3x2(-2.f * z, w, H23, M23, L23);
-                // K 6d..6d+5: uh, uh, um, uh, ul, um; K 18..20: wh, wm, wl
-                r0 = make_uint4(bf_pair<0, 0>(H01, H01), bf_pair<0, 0>(M01, H01), bf_pair<0, 0>(L01, M01),
-                                bf_pair<1, 1>(H01, H01));
-                r1 = make_uint4(bf_pair<1, 1>(M01, H01), bf_pair<1, 1>(L01, M01), bf_pair<0, 0>(H23, H23),
-                                bf_pair<0, 0>(M23, H23));
-                r2 = make_uint4(bf_pair<0, 0>(L23, M23), bf_pair<1, 1>(H23, M23), L23 >> 16, 0u);
-            }
-            sA[4 * p + 0] = r0;
-            sA[4 * p + 1] = r1;
-            sA[4 * p + 2] = r2;
-            sA[4 * p + 3] = make_uint4(0u, 0u, 0u, 0u);
+        if (p < ntp) {  // a row's 16-byte stores back to back
+            sA[rowslot(p, 0)] = rows[r][0];
+            sA[rowslot(p, 1)] = rows[r][1];
+            sA[rowslot(p, 2)] = rows[r][2];
         }
     }
     {
@@ -950,30 +1027,54 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     const int quarter = wave >> 1, half = wave & 1;
     const int g = lane >> 4, col = lane & 15;
     constexpr int QT = QW / 2 / 16;  // query tiles per wave
+    // lane group 3 (K 24..31) reads zeros whatever the tile: its tile steps are 0
+    const uint4 *pq = g < 3 ? sQB + 48 * half * QT + lane : sZ + col;
+    const uint4 *pa = g < 3 ? sA + lane : sZ + col;
+    const int tstep = g < 3 ? 48 : 0;
     pcm_bf16x8 bq[QT];
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-        const uint4 v = sQB[4 * (half * (QW / 2) + qt * 16 + col) + g];
-        bq[qt] = __builtin_bit_cast(pcm_bf16x8, v);
-    }
+    for (int qt = 0; qt < QT; ++qt) bq[qt] = __builtin_bit_cast(pcm_bf16x8, pq[qt * tstep]);
     float best[QT], sec[QT];
     int bchunk[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) { best[qt] = PCM_INF; sec[qt] = PCM_INF; bchunk[qt] = 0; }
     const int ngroups = ntp >> 6;
+    // software-pipelined: the four A tiles (one ds_read_b128 each) of the
+    // wave's next group are read while the current group is screened (the
+    // wave's last group re-reads itself)
+    uint4 an[4];
+    // (lane group 3: the tile offset 48 i inside the zero region, no group step)
+    auto fetch = [&](int gi, int i) { an[i] = pa[4 * gi * tstep + 48 * i]; };
+    if (quarter < ngroups) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fetch(quarter, i);
+    }
     for (int gi = quarter; gi < ngroups; gi += 4) {
+        const int gn = gi + 4 < ngroups ? gi + 4 : gi;
         float mn[QT];
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) mn[qt] = PCM_INF;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const uint4 av = sA[4 * (64 * gi + 16 * i + col) + g];
-            const pcm_bf16x8 a = __builtin_bit_cast(pcm_bf16x8, av);
+            const pcm_bf16x8 a = __builtin_bit_cast(pcm_bf16x8, an[i]);
+            // the next group's tile i is read before this tile's eight MFMAs
+            // (hipcc otherwise sinks the read to its use): one read per eight
+            // MFMAs, a whole group ahead
+            fetch(gn, i);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt) {
                 const pcm_f4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[qt], pcm_f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
                 mn[qt] = __builtin_fminf(__builtin_fminf(mn[qt], d.x), d.y);
                 mn[qt] = __builtin_fminf(__builtin_fminf(mn[qt], d.z), d.w);
+            }
+            // one MFMA, then the two folds of an earlier one: the folds sit in
+            // the MFMAs' 16-cycle gaps and read results that have already landed
+            __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
+#pragma unroll
+            for (int k = 0; k < QT - 2; ++k) {
+                __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
             }
         }
         const int cid = 4 * gi + g;
@@ -985,159 +1086,156 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     }
     __syncthreads();  // every wave is done reading sA / sQB
     PCM_STAMP(3);
-    // raw tile for the rescans (this thread's staged targets), partials
+    // raw tile for the rescans (this thread's staged targets)
 #pragma unroll
     for (int r = 0; r < kPer; ++r) {
         const int p = tid + r * NT;
         if (p < nt) { sT[0][mslot(p)] = tv[r][0]; sT[1][mslot(p)] = tv[r][1]; sT[2][mslot(p)] = tv[r][2]; }
     }
-    // the four lane groups of a wave hold the same queries: fold them (xor 16,
-    // xor 32) so one partial per (quarter, query) goes to LDS
+    // the four lane groups of a wave hold the same 8 query tiles against
+    // different chunks: two halving steps leave lane group g with the folded
+    // partials of tiles 4 (g >> 1) + 2 (g & 1) + {0, 1}; one partial per
+    // (quarter, query) to LDS
+    static_assert(QT == 8, "two halving steps: 8 query tiles -> 2 per lane");
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
+    for (int j = 0; j < 4; ++j)
+        mfma_fold_step<true>(best[j], sec[j], bchunk[j], best[j + 4], sec[j + 4], bchunk[j + 4]);
 #pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-            const float vb = __shfl_xor(best[qt], o, 64), vs = __shfl_xor(sec[qt], o, 64);
-            const int vc = __shfl_xor(bchunk[qt], o, 64);
-            const bool better = (vb < best[qt]) | ((vb == best[qt]) & (vc < bchunk[qt]));
-            sec[qt] = __builtin_fminf(__builtin_fminf(sec[qt], vs), better ? best[qt] : vb);
-            best[qt] = better ? vb : best[qt];
-            bchunk[qt] = better ? vc : bchunk[qt];
-        }
-        if (g == 0) {
-            const int s = half * (QW / 2) + qt * 16 + col;
-            sPB[quarter][s] = best[qt];
-            sPS[quarter][s] = sec[qt];
-            sPC[quarter][s] = bchunk[qt];
-        }
+    for (int j = 0; j < 2; ++j) {
+        mfma_fold_step<false>(best[j], sec[j], bchunk[j], best[j + 2], sec[j + 2], bchunk[j + 2]);
+        const int s = half * (QW / 2) + (4 * (g >> 1) + 2 * (g & 1) + j) * 16 + col;
+        sPB[quarter][s] = best[j];
+        sPS[quarter][s] = sec[j];
+        sPC[quarter][s] = bchunk[j];
     }
-    static_assert(kMfmaNT / 64 == W, "one vote slot per wave of the MFMA forward");
-    __shared__ int sNFm[kMfmaNT / 64];
-    const int any_nonfinite = pcm_wg_or(nonfinite, sNFm, kMfmaNT / 64);
+    const int any_nonfinite = pcm_wg_or(nonfinite, sNFm, W);
+    PCM_STAMP(4);
 
     float my_d = 0.f;
     if (!any_nonfinite) {
-        // ---- merge the 16 partials; proof
-        if (tid < QW) {
-            float fb = sPB[0][tid], fs = sPS[0][tid];
-            int fc = sPC[0][tid];
-#pragma unroll
-            for (int p = 1; p < 4; ++p) {
-                const float vb = sPB[p][tid], vs = sPS[p][tid];
-                const int vc = sPC[p][tid];
-                const bool better = (vb < fb) | ((vb == fb) & (vc < fc));
-                fs = __builtin_fminf(__builtin_fminf(fs, vs), better ? fb : vb);
-                fb = better ? vb : fb;
-                fc = better ? vc : fc;
-            }
-            float rmax2 = sRmax[0];
-#pragma unroll
-            for (int w = 1; w < W; ++w) rmax2 = __builtin_fmaxf(rmax2, sRmax[w]);
-            const float x = qx - c0, y = qy - c1, z = qz - c2;
-            const float qn2 = __builtin_fmaf(z, z, __builtin_fmaf(y, y, x * x));
-            const float rr = __builtin_sqrtf(rmax2) + __builtin_sqrtf(qn2);
-            const float e2 = 2.f * (kFiltU80 * (rr * rr) * 1.001f + 7.888609052210118e-31f);  // + 2^-100
-            if ((fs - fb) > e2) {  // false for NaN
-                sFc[tid] = fc;
-            } else {
-                // near-tie plan, -1 - bits: quarter q is scanned whole (bit q)
-                // when its second-best chunk may lie within fb + 2E, else its
-                // best chunk alone (bit 4 + q) when that one may; every other
-                // candidate screens above fb + 2E, so lies above the answer.
-                // NaN anywhere selects the scan.
-                const float thr = fb + e2;
-                int plan = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (!(sPS[q][tid] > thr)) plan |= 1 << q;
-                    else if (!(sPB[q][tid] > thr)) plan |= 16 << q;
-                }
-                sFc[tid] = -1 - plan;
-            }
-        }
-        __syncthreads();
-        PCM_STAMP(4);
-        // ---- exact rescan of the proven chunk: thread = (query slot s, part):
-        // part p takes tiles 2p, 2p + 1 of the group, rows 4g..4g+3 (ascending)
+        // ---- one pass, one barrier: thread (s = tid mod QW, part = tid / QW)
+        // merges the four quarters' partials of query s -- both parts reach
+        // the same verdict -- and, when the best chunk is proven, rescans its
+        // half of that chunk exactly (tiles 2 part, 2 part + 1 of the group,
+        // rows 4g..4g+3, ascending); part 0 of a near-tie query lists it with
+        // its plan instead.
+        const int s = tid & (QW - 1), part = tid / QW;
+        bool proven = false;
         {
-            const int s = tid % QW, part = tid / QW;
-            const int fc = sFc[s];
+            float vb[4], vs[4], vr[W];
+            int vc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {  // every load first, then branch-free selects
+                vb[q] = sPB[q][s];
+                vs[q] = sPS[q][s];
+                vc[q] = sPC[q][s];
+            }
+#pragma unroll
+            for (int w = 0; w < W; ++w) vr[w] = sRmax[w];
+            __builtin_amdgcn_sched_barrier(0);
+            float fb = vb[0], fs = vs[0];
+            int fc = vc[0];
+#pragma unroll
+            for (int q = 1; q < 4; ++q) {
+                const bool better = (vb[q] < fb) | ((vb[q] == fb) & (vc[q] < fc));
+                fs = __builtin_fminf(__builtin_fminf(fs, vs[q]), better ? fb : vb[q]);
+                fb = better ? vb[q] : fb;
+                fc = better ? vc[q] : fc;
+            }
+            float rmax2 = vr[0];
+#pragma unroll
+            for (int w = 1; w < W; ++w) rmax2 = __builtin_fmaxf(rmax2, vr[w]);
+            // the bound E of the header with R = max |t'| for every target (eR),
+            // and, as filt_forward argues it, with |t'| <= |q'| + sqrt(d_b) for
+            // every target that can reach the best chunk's exact minimum d_b
+            // <= fb + |q'|^2 + eR: E <= 80u (2|q'| + sqrt(db))^2
+            const float kAbs = 7.888609052210118e-31f;  // 2^-100
+            const float qn2 = __builtin_fmaf(qzc, qzc, __builtin_fmaf(qyc, qyc, qxc * qxc));
+            const float sq = __builtin_amdgcn_sqrtf(qn2);
+            const float rr = __builtin_amdgcn_sqrtf(rmax2) + sq;
+            const float eR = kFiltU80 * (rr * rr) * 1.001f + kAbs;
+            const float db = __builtin_fmaxf((fb + qn2) * 1.0001f + 2.f * eR, 0.f);
+            const float rq = 2.f * sq + __builtin_amdgcn_sqrtf(db);
+            const float e2 = 2.f * (kFiltU80 * __builtin_fminf(rr * rr, rq * rq) * 1.001f + kAbs);
+            proven = (fs - fb) > e2;  // false for NaN
             float hd = PCM_INF;
             int hk = 0x7fffffff;
-            if (qbase + s < nq && fc >= 0) {
-                const float x = sQx[s], y = sQy[s], z = sQz[s];
-                const int k0 = 64 * (fc >> 2) + 32 * part + 4 * (fc & 3);
-                float tx[8], ty[8], tz[8];
+            if (qbase + s < nq) {
+                if (proven) {
+                    // two quads of the raw tile, 16 targets apart; a quad stays
+                    // contiguous under mslot, and slots past nt (inside the last
+                    // 64-target group) hold stale bytes that `take` ignores
+                    const int k0 = 64 * (fc >> 2) + 32 * part + 4 * (fc & 3);
+                    pcm_f4 tx[2], ty[2], tz[2];
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int kk = mslot(min(k0 + 16 * (k >> 2) + (k & 3), nt - 1));
-                    tx[k] = sT[0][kk];
-                    ty[k] = sT[1][kk];
-                    tz[k] = sT[2][kk];
-                }
+                    for (int h = 0; h < 2; ++h) {
+                        const int o = mslot(k0 + 16 * h);
+                        tx[h] = *reinterpret_cast<const pcm_f4 *>(&sT[0][o]);
+                        ty[h] = *reinterpret_cast<const pcm_f4 *>(&sT[1][o]);
+                        tz[h] = *reinterpret_cast<const pcm_f4 *>(&sT[2][o]);
+                    }
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int kk = k0 + 16 * (k >> 2) + (k & 3);
-                    const float d = pcm_sqd(tx[k] - x, ty[k] - y, tz[k] - z);
-                    const bool take = (d < hd) & (kk < nt);
-                    hd = take ? d : hd;
-                    hk = take ? kk : hk;
+                    for (int k = 0; k < 8; ++k) {  // ascending: strict '<' keeps the lowest
+                        const int kk = k0 + 16 * (k >> 2) + (k & 3);
+                        const float d = pcm_sqd(tx[k >> 2][k & 3] - qx, ty[k >> 2][k & 3] - qy, tz[k >> 2][k & 3] - qz);
+                        const bool take = (d < hd) & (kk < nt);
+                        hd = take ? d : hd;
+                        hk = take ? kk : hk;
+                    }
+                } else if (part == 0) {
+                    // near-tie plan: quarter q is scanned whole (bit q) when its
+                    // second-best chunk may lie within fb + 2E, else its best
+                    // chunk alone (bit 4 + q) when that one may; every other
+                    // candidate screens above fb + 2E, so lies above the
+                    // answer.  NaN anywhere selects the scan.
+                    const float thr = fb + e2;
+                    unsigned plan = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) plan |= !(vs[q] > thr) ? (1u << q) : (!(vb[q] > thr) ? (16u << q) : 0u);
+                    sPlan[s] = plan;
+                    sList[atomicAdd(&sNList, 1)] = s;
                 }
             }
             sHD[part][s] = hd;
             sHK[part][s] = hk;
         }
         __syncthreads();
-        if (tid < QW && qbase + tid < nq) {
-            if (sFc[tid] >= 0) {
-                float d = sHD[0][tid];
-                int k = sHK[0][tid];
-                pcm_lexmin(d, k, sHD[1][tid], sHK[1][tid]);
-                sD[tid] = d;
-                sK[tid] = k;
-            } else {
-                sList[atomicAdd(&sNList, 1)] = tid;
-            }
-        }
-        __syncthreads();
         PCM_STAMP(5);
-        // ---- near-ties: one wave per query, exact scan of the plan's
-        // candidates (64-target groups of whole quarters, single chunks)
+        // ---- near-ties: one wave per listed query, exact scan of the plan's
+        // candidates only.  One step takes the four quarters' single chunks
+        // (lane group q: the 16 targets of quarter q's best chunk); a whole
+        // quarter is its up to four 64-target groups, one target per lane each.
         const int nl = sNList;
-#ifdef PCM_STAMPS
-        if (tid == 0 && blockIdx.x < kStampSlots) {  // diagnostics: ties, whole quarters, single chunks
-            unsigned long long full = 0, single = 0;
-            for (int e = 0; e < nl; ++e) {
-                const int pl = -1 - sFc[sList[e]];
-                full += __popc(pl & 15);
-                single += __popc((pl >> 4) & 15);
-            }
-            g_pcm_stamps[blockIdx.x * 8 + 0] = (unsigned long long)nl | (full << 16) | (single << 40);
-        }
-#endif
         for (int e = wave; e < nl; e += W) {
-            const int s = sList[e];
-            const int plan = -1 - sFc[s];
-            const float x = sQx[s], y = sQy[s], z = sQz[s];
+            const int sq = __builtin_amdgcn_readfirstlane(sList[e]);
+            const unsigned plan = __builtin_amdgcn_readfirstlane(sPlan[sq]);
+            float x = rx[0], y = ry[0], z = rz[0];
+#pragma unroll
+            for (int qq = 1; qq < QPT; ++qq)
+                if ((sq >> 6) == qq) { x = rx[qq]; y = ry[qq]; z = rz[qq]; }
+            // sq is wave-uniform: v_readlane, not an LDS permute round trip
+            x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), sq & 63));
+            y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y), sq & 63));
+            z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), sq & 63));
             float bd = PCM_INF;
             int bk = 0x7fffffff;
-            for (int gi0 = 0; gi0 < ngroups; gi0 += 4) {  // 4 groups in flight, one candidate each per lane
+            {
+                const int pc = sPC[g][sq];
+                const int k = 64 * (pc >> 2) + 16 * (col >> 2) + 4 * (pc & 3) + (col & 3);
+                const bool on = ((plan >> (4 + g)) & 1u) && k < nt;
+                const int ks = mslot(min(k, nt - 1));
+                const float d = pcm_sqd(sT[0][ks] - x, sT[1][ks] - y, sT[2][ks] - z);
+                if (on) pcm_lexmin(bd, bk, d, k);
+            }
+            for (int q = 0; q < 4; ++q) {
+                if (!((plan >> q) & 1u)) continue;
                 float tx[4], ty[4], tz[4];
                 int kk[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int gi = gi0 + u, q = u;  // gi % 4 == u
-                    int k = -1;
-                    if (gi < ngroups) {
-                        if (plan & (1 << q)) {
-                            k = 64 * gi + lane;
-                        } else if ((plan & (16 << q)) && lane < 16) {
-                            const int pc = sPC[q][s];
-                            if ((pc >> 2) == gi) k = 64 * gi + 16 * (lane >> 2) + 4 * (pc & 3) + (lane & 3);
-                        }
-                    }
-                    kk[u] = (k >= 0 && k < nt) ? k : -1;
-                    const int ks = mslot(max(kk[u], 0));
+                for (int u = 0; u < 4; ++u) {  // the quarter's groups, all loads in flight
+                    const int k = 64 * (q + 4 * u) + lane;
+                    kk[u] = (q + 4 * u < ngroups && k < nt) ? k : -1;
+                    const int ks = mslot(min(max(kk[u], 0), nt - 1));
                     tx[u] = sT[0][ks];
                     ty[u] = sT[1][ks];
                     tz[u] = sT[2][ks];
@@ -1148,22 +1246,44 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
                     if (kk[u] >= 0) pcm_lexmin(bd, bk, d, kk[u]);
                 }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) pcm_lexmin(bd, bk, __shfl_xor(bd, o, 64), __shfl_xor(bk, o, 64));
+            pcm_wave_lexmin(bd, bk);
             if (lane == 0) {
-                sD[s] = bd;
-                sK[s] = bk;
+                sD[sq] = bd;
+                sK[sq] = bk;
             }
         }
         if (nl > 0) __syncthreads();
         PCM_STAMP(6);
 #ifdef PCM_STAMPS
         if (tid == 0 && blockIdx.x < 4096) g_pcm_stamps[(8192 + blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_memtime();
+        if (tid == NT - 1 && blockIdx.x < kStampSlots) {  // diagnostics: ties, whole quarters, single chunks
+            unsigned long long full = 0, single = 0;
+            for (int e = 0; e < nl; ++e) {
+                const unsigned pl = sPlan[sList[e]];
+                full += __popc(pl & 15);
+                single += __popc((pl >> 4) & 15);
+            }
+            g_pcm_stamps[blockIdx.x * 8 + 0] = (unsigned long long)nl | (full << 16) | (single << 40);
+        }
 #endif
+        // ---- outputs (thread tid < QW is part 0 of query tid: `proven` is that query's verdict)
         if (tid < QW && qbase + tid < nq) {
-            my_d = sD[tid];
-            out_st<kSc1>(D + qbase + tid, my_d);
-            out_st<kSc1>(I + qbase + tid, (int32_t)sK[tid]);
+            float d;
+            int k;
+            if (proven) {
+                d = sHD[0][tid];
+                k = sHK[0][tid];
+                pcm_lexmin(d, k, sHD[1][tid], sHK[1][tid]);
+            } else {
+                d = sD[tid];
+                k = sK[tid];
+            }
+            my_d = d;
+            out_st<kSc1>(D + qbase + tid, d);
+            out_st<kSc1>(I + qbase + tid, (int32_t)k);
+            // data-tagged argmin granule {call tag, idx}: one 8-byte sc1 store, its own flag
+            if (Gr) __hip_atomic_store(Gr + qbase + tid, tag | (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (kown) *kown = k;
         }
     } else {
         for (int s = tid; s < QW; s += NT) {
@@ -1171,11 +1291,13 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
             if (qi >= nq) continue;
             float d;
             int idx;
-            pcm_ref_nn_scan(pcm_ld(Q + 3 * (size_t)qi + 0), pcm_ld(Q + 3 * (size_t)qi + 1),
-                            pcm_ld(Q + 3 * (size_t)qi + 2), T, nt, d, idx);
+            pcm_ref_nn_scan(pcm_ld(Q + pcm_at(LQ, qi, 0)), pcm_ld(Q + pcm_at(LQ, qi, 1)),
+                            pcm_ld(Q + pcm_at(LQ, qi, 2)), T, nt, d, idx, LT);
             my_d = d;
             out_st<kSc1>(D + qi, d);
             out_st<kSc1>(I + qi, (int32_t)idx);
+            if (Gr) __hip_atomic_store(Gr + qi, tag | (unsigned)idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (kown) *kown = idx;
         }
     }
     return my_d;
@@ -2000,12 +2122,16 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
     float *__restrict__ dist1, float *__restrict__ dist2, int32_t *__restrict__ idx1, int32_t *__restrict__ idx2,
     float *__restrict__ mean_out, float *__restrict__ grad1, float *__restrict__ grad2, int nblk1, int nblk2,
     GradWs ws, unsigned max_spins, unsigned poll_spins, const float *__restrict__ gscale) {
-    static_assert((LAY1 == 0 && LAY2 == 0) || (kGran && !kMfma),
+    static_assert((LAY1 == 0 && LAY2 == 0) || kGran,
                   "channel planes: the granule forms (the LDS copies keep each cloud's layout)");
+    static_assert(!kMfma || !(kEarly || kLocal || kSplit || kG4 || kG4x),
+                  "the MFMA forward: counter or 8-byte granule hand-off, both clouds copied in for the gradients");
     constexpr int QW = 64 * QPT;
     constexpr int NT = 64 * W;
     static_assert(!kMfma || (W == 8 && QPT == 4 && TILE == kMfmaTile), "the MFMA forward's fixed geometry");
     constexpr int kFwd = kMfma ? MfmaLds::kBytes : FiltLds<W, QPT, TILE>::kBytes;
+    static_assert(!kMfma || kFwd <= kGradBytes,
+                  "two workgroups' LDS per CU: the polling workgroup runs beside the forward workgroups from the start");
     // kEarly: the gradient phase's clouds get an LDS region of their own, so
     // their copy is issued before the scan instead of after the forward
     // kLocal: the gradient phase reads the forward's own LDS data (its
@@ -2072,7 +2198,14 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
         // 16-byte granule stores when every row start is 16-byte aligned
         const bool g4x = kG4x && ((n | m) & 3) == 0;
         float my_d;
-        if constexpr (LAY1 == LAY2) {
+        if constexpr (kMfma) {
+            // one inlined forward: the layouts reach its prologue loads only
+            my_d = filt_forward_mfma<false>(first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
+                                            first ? dist1 + (size_t)batch * n : dist2 + (size_t)batch * m,
+                                            first ? idx1 + (size_t)batch * n : idx2 + (size_t)batch * m, arena,
+                                            first ? G1 : G2, tag, first ? L1 : L2, first ? L2 : L1,
+                                            kOwnK ? &myk : nullptr);
+        } else if constexpr (LAY1 == LAY2) {
             const PcmLay LQ = LAY1 ? PcmLay{1, first ? n : m} : PcmLay{3, 1};
             my_d = filt_forward<float, W, QPT, C, TILE, false, kSplit>(
                 first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
@@ -2357,8 +2490,12 @@ struct GradVariant {
 // fastest in every state: 13.09-13.12 vs 13.44-13.49 us in tools/ab_chamfer.py
 // and 15.48-15.72 vs 15.79-15.99 us per step in the bench's own command
 // (profiles/r06/bench_variants_r06zk_zl.txt)
-constexpr int kDefaultGradVariant = 7;
-#define PCM_GRAD_DEFAULT(L1, L2) chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, false, false, false, false, false, L1, L2>
+// Since then: variant 19, 7's hand-off and gradient phase behind the
+// matrix-core screen (filt_forward_mfma), for every size the entry takes
+// (n, m <= 1024): 12.4 against 13.65 us in tools/ab_chamfer.py, the bench's
+// own figures in DESIGN.md section 3.5c (profiles/mfma_screen/).
+constexpr int kDefaultGradVariant = 19;
+#define PCM_GRAD_DEFAULT(L1, L2) chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, L1, L2>
 // The product library holds the default only; the measured alternatives are
 // compiled into the tuning build (make tune: -DPCM_TUNE, libpcm_hip_tune.so),
 // which tools/ and the variant tests load.
@@ -2371,7 +2508,8 @@ const GradVariant kGradVariants[] = {
     {4, chamfer_loss_grad_kernel<8, 4, 32, 1024>, 8, 4},
     {5, chamfer_loss_grad_kernel<16, 4, 32, 1024>, 16, 4},
     {6, chamfer_loss_grad_kernel<8, 4, 16, 1024, true>, 8, 4},  // screen on the matrix cores
-    // 7: the granule hand-off (the default, below)
+    // 7: the granule hand-off behind the VALU screen (filt_forward); the default until 19
+    {7, chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true>, 8, 4},
     {8, chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, true>, 8, 4},  // 7 + the clouds copied during the scan
     {9, chamfer_loss_grad_kernel<8, 4, 8, 1024, false, true>, 8, 4},   // 7 with 8-candidate chunks
     {10, chamfer_loss_grad_kernel<8, 4, 32, 1024, false, true>, 8, 4},  // 7 with 32-candidate chunks
@@ -2399,17 +2537,20 @@ const GradVariant kGradVariants[] = {
     // own-range granule reads)
     {18, chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, false, false, false, false, false, 0, 0, false, true>, 8, 4},
 #endif
+    // 19 (the default): 7's hand-off and gradient phase behind the matrix-core screen (filt_forward_mfma)
     {kDefaultGradVariant, PCM_GRAD_DEFAULT(0, 0), 8, 4},
 };
 // the default variant with cloud 1 / cloud 2 in channel planes (index 2 lay1 + lay2)
 const grad_kernel_t kGradDefaultLay[4] = {PCM_GRAD_DEFAULT(0, 0), PCM_GRAD_DEFAULT(0, 1), PCM_GRAD_DEFAULT(1, 0),
                                           PCM_GRAD_DEFAULT(1, 1)};
 #ifdef PCM_TUNE
-// the mixed-layout instances with one inlined forward (strides in registers)
+// the mixed-layout instances with one inlined forward (strides in registers):
+// the matrix-core forward is always inlined once, so kLayOne changes nothing
+// in it and the instances stay only so that lay_form 1 keeps its meaning
 const grad_kernel_t kGradLayOne[4] = {
     PCM_GRAD_DEFAULT(0, 0),
-    chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, false, false, false, false, false, 0, 1, true>,
-    chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, false, false, false, false, false, 1, 0, true>,
+    chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, 0, 1, true>,
+    chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, 1, 0, true>,
     PCM_GRAD_DEFAULT(1, 1)};
 #endif
 #undef PCM_GRAD_DEFAULT
@@ -2422,6 +2563,7 @@ const grad_kernel_t kGradLayOne[4] = {
 // their own while staging, one barrier after the scan instead of two -- 13.28
 // against 13.16 us, profiles/r04/chamfer_sept_r04q_ab.txt)
 constexpr int kNumGradVariants = sizeof(kGradVariants) / sizeof(kGradVariants[0]);
+constexpr int kMaxTuneVariantId = 19;  // the highest id of the tuning build's table above
 // tools/tune_chamfer.py (profiles/r01): B=32, N=M=1024 -- W=8 QPT=4 18.7 us,
 // W=8 QPT=2 19.3 us, W=4 QPT=2 21.4 us; round 2: variant 1 (arrival counter
 // hand-off) 16.25 us, variant 7 (the same forward, granule hand-off) 14.97 us
@@ -2455,6 +2597,10 @@ long long grad_blocks_max(int b, int n, int m) {
     return most;
 }
 
+// the matrix-core forward takes single-tile clouds (n, m <= kMfmaTile): that is
+// the entry's own limit (kGradCap, checked by launch_loss_grad), so 19 serves
+// every size the entry accepts
+static_assert(kMfmaTile >= kGradCap, "the default serves every size the entry takes");
 int default_grad_variant(int, int, int) { return kDefaultGradVariant; }
 
 int launch_loss_grad(int variant, const float *xyz1, const float *xyz2, int b, int n, int m, float w1, float w2,
@@ -2466,7 +2612,8 @@ int launch_loss_grad(int variant, const float *xyz1, const float *xyz2, int b, i
     if (n > kGradCap || m > kGradCap) return PCM_ERR_UNSUPPORTED;
     if ((unsigned)lay1 > 1u || (unsigned)lay2 > 1u) return PCM_ERR_INVALID_ARG;
     const GradVariant *v = find_grad_variant(variant);
-    if (!v) return variant >= 0 && variant <= 18 ? PCM_ERR_UNSUPPORTED : PCM_ERR_INVALID_ARG;  // all but 7: tuning build
+    // a known id this build does not hold (all but the default: tuning build)
+    if (!v) return variant >= 0 && variant <= kMaxTuneVariantId ? PCM_ERR_UNSUPPORTED : PCM_ERR_INVALID_ARG;
     if ((lay1 | lay2) && variant != kDefaultGradVariant) return PCM_ERR_UNSUPPORTED;
     if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2 || !mean_out || !grad1 || !grad2 || !workspace)
         return PCM_ERR_INVALID_ARG;

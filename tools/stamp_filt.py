@@ -19,6 +19,9 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["PCM_HIP_LIB"] = os.environ.get(
     "PCM_STAMPS_LIB", os.path.join(REPO, "3d-pointcloudreconstruction_amd", "lib", "libpcm_hip_stamps.so"))
+# the stamps build holds every tuning variant (-DPCM_TUNE): numbered variants
+# must run from it too, not from libpcm_hip_tune.so, or no stamp is written
+os.environ["PCM_HIP_TUNE_LIB"] = os.environ["PCM_HIP_LIB"]
 sys.path.insert(0, os.path.join(REPO, "3d-pointcloudreconstruction_amd", "metric"))
 import torch  # noqa: E402
 import pcm_hip  # noqa: E402
@@ -128,7 +131,7 @@ def run_fused(v, b, n, m, dev):
           f"{statistics.median(spread):.2f} max {max(spread):.2f} us")
     # the forward's own stamps (table's lower half, same workgroup numbering)
     lo = [[buf[i * 8 + k] for k in range(8)] for i in range(nblk - 1)]
-    if v == 6:  # the matrix-core forward stores its near-tie census in slot 0
+    if v in (6, 19):  # the matrix-core forward stores its near-tie census in slot 0
         nl = [r[0] & 0xffff for r in lo]
         full = sum((r[0] >> 16) & 0xffffff for r in lo)
         single = sum(r[0] >> 40 for r in lo)
@@ -154,7 +157,7 @@ def run_fused(v, b, n, m, dev):
               f"max {max(dur):7.2f}  (>1 us: {sum(d > 1.0 for d in dur)} workgroups)")
 
 
-FUSED_QPT = [2, 4, 2, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4]          # csrc/chamfer_filt.hip kGradVariants
+FUSED_QPT = [2, 4, 2] + [4] * 17                                   # csrc/chamfer_filt.hip kGradVariants
 
 
 def main():
