@@ -898,6 +898,8 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     float(*sPB)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4);
     float(*sPS)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4 + 4 * QW * 4);
     int(*sPC)[QW] = reinterpret_cast<int(*)[QW]>(arena + 3 * TILE * 4 + 8 * QW * 4);
+    float(*sQR)[QW] = reinterpret_cast<float(*)[QW]>(arena + MfmaLds::kTail);  // raw queries (after the scan)
+    static_assert(MfmaLds::kTail + 3 * QW * 4 <= MfmaLds::kBytes, "raw queries fit the arena behind the partials");
     __shared__ float sD[QW];  // near-tie results
     __shared__ int sK[QW];
     __shared__ unsigned sPlan[QW];
@@ -1039,9 +1041,9 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) { best[qt] = PCM_INF; sec[qt] = PCM_INF; bchunk[qt] = 0; }
     const int ngroups = ntp >> 6;
-    // software-pipelined: the four A tiles (one ds_read_b128 each) of the
-    // wave's next group are read while the current group is screened (the
-    // wave's last group re-reads itself)
+    // software-pipelined: each of the four A tiles (one ds_read_b128 each)
+    // is read for the wave's next group while the current group is screened
+    // (the wave's last group re-reads itself)
     uint4 an[4];
     // (lane group 3: the tile offset 48 i inside the zero region, no group step)
     auto fetch = [&](int gi, int i) { an[i] = pa[4 * gi * tstep + 48 * i]; };
@@ -1049,41 +1051,57 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
 #pragma unroll
         for (int i = 0; i < 4; ++i) fetch(quarter, i);
     }
+    // A group's 32 MFMAs (tile i = k / 8 against query tile k mod 8) are one
+    // sequence over kRot rotating result quads: MFMA k, then the two folds of
+    // MFMA k - kLag, whose result has landed by then, so no MFMA waits for a
+    // fold and no fold for its MFMA.  The sequence runs on across the groups:
+    // a group's last kLag results are folded behind the next group's first
+    // MFMAs (before the wave's first group the quads hold +inf), and the
+    // best/second/chunk update of the group before sits in the first eight
+    // gaps, behind those folds and ahead of each query tile's first fold of
+    // this group (mn = +inf before the first group: that update changes
+    // nothing).  The last group's folds and update follow the loop.  A query
+    // tile's folds stay in tile order 0..3.  Tile i is re-read in place for
+    // the next group right after its eight MFMAs: one read per eight MFMAs,
+    // no second buffer and no copy.  A fence behind every MFMA and behind its
+    // gap's folds pins this order (left to itself hipcc puts some folds ahead
+    // of their gap's MFMA, one instruction short of the result's latency).
+    constexpr int kRot = 4, kLag = 3;
+    float mn[QT];
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) mn[qt] = PCM_INF;
+    pcm_f4 d[kRot];
+#pragma unroll
+    for (int r = 0; r < kRot; ++r) d[r] = pcm_f4{PCM_INF, PCM_INF, PCM_INF, PCM_INF};
+    int cid = 0;  // chunk of the group whose mins mn holds
+    auto fold = [&](int k, bool first) {  // (a group's first fold of a query tile starts from +inf)
+        const pcm_f4 r = d[k % kRot];
+        mn[k % QT] = __builtin_fminf(__builtin_fminf(first ? PCM_INF : mn[k % QT], r.x), r.y);
+        mn[k % QT] = __builtin_fminf(__builtin_fminf(mn[k % QT], r.z), r.w);
+    };
+    auto update = [&](int qt) {
+        sec[qt] = __builtin_amdgcn_fmed3f(mn[qt], best[qt], sec[qt]);
+        if (mn[qt] < best[qt]) { best[qt] = mn[qt]; bchunk[qt] = cid; }
+    };
     for (int gi = quarter; gi < ngroups; gi += 4) {
         const int gn = gi + 4 < ngroups ? gi + 4 : gi;
-        float mn[QT];
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) mn[qt] = PCM_INF;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const pcm_bf16x8 a = __builtin_bit_cast(pcm_bf16x8, an[i]);
-            // the next group's tile i is read before this tile's eight MFMAs
-            // (hipcc otherwise sinks the read to its use): one read per eight
-            // MFMAs, a whole group ahead
-            fetch(gn, i);
+        for (int k = 0; k < 4 * QT; ++k) {
+            d[k % kRot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pcm_bf16x8, an[k / QT]), bq[k % QT],
+                                                                  pcm_f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            if (k % QT == QT - 1) fetch(gn, k / QT);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                const pcm_f4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq[qt], pcm_f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                mn[qt] = __builtin_fminf(__builtin_fminf(mn[qt], d.x), d.y);
-                mn[qt] = __builtin_fminf(__builtin_fminf(mn[qt], d.z), d.w);
-            }
-            // one MFMA, then the two folds of an earlier one: the folds sit in
-            // the MFMAs' 16-cycle gaps and read results that have already landed
-            __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
-#pragma unroll
-            for (int k = 0; k < QT - 2; ++k) {
-                __builtin_amdgcn_sched_group_barrier(0x2, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-            }
+            if (k < kLag) fold(4 * QT - kLag + k, false);
+            else fold(k - kLag, k - kLag < QT);
+            if (k < QT) update(k);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        const int cid = 4 * gi + g;
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-            sec[qt] = __builtin_amdgcn_fmed3f(mn[qt], best[qt], sec[qt]);
-            if (mn[qt] < best[qt]) { best[qt] = mn[qt]; bchunk[qt] = cid; }
-        }
+        cid = 4 * gi + g;
     }
+#pragma unroll
+    for (int k = 4 * QT - kLag; k < 4 * QT; ++k) fold(k, false);
+#pragma unroll
+    for (int qt = 0; qt < QT; ++qt) update(qt);
     __syncthreads();  // every wave is done reading sA / sQB
     PCM_STAMP(3);
     // raw tile for the rescans (this thread's staged targets)
@@ -1092,6 +1110,10 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
         const int p = tid + r * NT;
         if (p < nt) { sT[0][mslot(p)] = tv[r][0]; sT[1][mslot(p)] = tv[r][1]; sT[2][mslot(p)] = tv[r][2]; }
     }
+    // and the raw queries for the near-tie pass (thread tid < QW holds query
+    // tid): the per-wave register copies rx, ry, rz end at the query split, so
+    // the screen loop does not carry them
+    if (tid < QW) { sQR[0][tid] = qx; sQR[1][tid] = qy; sQR[2][tid] = qz; }
     // the four lane groups of a wave hold the same 8 query tiles against
     // different chunks: two halving steps leave lane group g with the folded
     // partials of tiles 4 (g >> 1) + 2 (g & 1) + {0, 1}; one partial per
@@ -1209,14 +1231,8 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
         for (int e = wave; e < nl; e += W) {
             const int sq = __builtin_amdgcn_readfirstlane(sList[e]);
             const unsigned plan = __builtin_amdgcn_readfirstlane(sPlan[sq]);
-            float x = rx[0], y = ry[0], z = rz[0];
-#pragma unroll
-            for (int qq = 1; qq < QPT; ++qq)
-                if ((sq >> 6) == qq) { x = rx[qq]; y = ry[qq]; z = rz[qq]; }
-            // sq is wave-uniform: v_readlane, not an LDS permute round trip
-            x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), sq & 63));
-            y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y), sq & 63));
-            z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(z), sq & 63));
+            // sq is wave-uniform: one broadcast read each, beside the plan's
+            const float x = sQR[0][sq], y = sQR[1][sq], z = sQR[2][sq];
             float bd = PCM_INF;
             int bk = 0x7fffffff;
             {
