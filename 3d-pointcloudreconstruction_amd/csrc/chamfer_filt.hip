@@ -795,7 +795,31 @@ __device__ __forceinline__ float filt_forward(const TIn *__restrict__ Q, const T
 // by (query, part) threads, near ties listed with a plan and rescanned by one
 // wave each over the planned chunks only, and the per-query bound: E above
 // with (R + |q'|)^2 replaced by min((R + |q'|)^2, (2|q'| + sqrt(d_b))^2), by
-// filt_forward's argument.  The one-launch step's default (fused variant 19).
+// filt_forward's argument.  Fused variants 6 and 19.
+//
+// The wide form (kWide; the one-launch step's default, fused variant 20) runs
+// the same screen on v_mfma_f32_32x32x16_bf16: an MFMA holds its SIMD's vector
+// issue for 8 cycles whatever its shape, so 1024 values per instruction
+// instead of 256 halve the MFMA issue slots of the loop, which is bound by
+// vector issue, not by the matrix pipe.  Staging, the LDS image, the arena and
+// the proof are the narrow form's.  A = 32 targets x 16 K, B = 16 K x 32
+// queries, two chained MFMAs per (A tile, query tile): K 0..15 onto an inline
+// zero, then K 16..31 onto that result in place.  Lane l receives
+// D[targets 8 j + 4 (l >> 5) + r][query l & 31] in element 4 j + r: sixteen
+// candidates of ONE query, folded with eight v_min3 and no cross-lane work.
+// Wave (quarter, half): the half's 128 queries are four tiles of 32 (their
+// eight B operands stay in registers), a 64-target group is two A tiles.  A
+// chunk is one A tile seen by one lane half -- targets
+// 64 g + 32 i + 8 j + 4 h + r, id 4 g + 2 i + h -- still 16 candidates, 64 ids
+// per 1024 targets and four chunks per quarter and group, so the merge, the
+// proof and the plans are unchanged; only the maps from a chunk id to its
+// candidates (exact rescan, near-tie single-chunk step) differ.
+// The error bound is unchanged: the 21 live K slots are K 0..15 in the first
+// MFMA and K 16..20 in the second, their products are the same exact ones,
+// adding the zero C is exact, and the 20 fp32 additions "in any order,
+// rounding or truncating" are the same 20 (tests/test_mfma_wide_bound_cpu.py
+// restates them in several orders).  Pad rows (wh = +inf at K 18) and an
+// overflowed w screen as in the narrow form.
 // ---------------------------------------------------------------------------
 constexpr float kFiltU80 = 4.76837158203125e-06f;  // 80 u = 80 * 2^-24
 constexpr int kMfmaQW = 256, kMfmaNT = 512, kMfmaTile = 1024;
@@ -818,6 +842,7 @@ struct MfmaLds {
     static constexpr int kBytes = kScan > kTail ? kScan : kTail;
 };
 typedef __bf16 pcm_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float pcm_f16v __attribute__((ext_vector_type(16)));  // a 32 x 32 MFMA result: 16 rows of the lane's column
 
 typedef __bf16 pcm_bf16x2 __attribute__((ext_vector_type(2)));
 // (a, b) -> one dword of two round-to-nearest-even bf16 (v_cvt_pk_bf16_f32): a low, b high
@@ -881,7 +906,7 @@ __device__ __forceinline__ void mfma_fold_step(float &b, float &s, int &c, float
 // filt_forward publishes them); kown: the thread's own argmin; LQ / LT: the
 // clouds' layouts (prologue loads only: everything after works on registers
 // and LDS).
-template <bool kSc1>
+template <bool kSc1, bool kWide = false>
 __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, const float *__restrict__ T, int nq,
                                                    int nt, int qbase, float *__restrict__ D, int32_t *__restrict__ I,
                                                    unsigned char *arena, unsigned long long *__restrict__ Gr = nullptr,
@@ -1024,6 +1049,9 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     }
     __syncthreads();
     PCM_STAMP(2);
+#ifdef PCM_STAMPS
+    if (tid == 0 && blockIdx.x < 4096) g_pcm_stamps[(8192 + blockIdx.x) * 8 + 2] = __builtin_amdgcn_s_memtime();
+#endif
 
     // ---- screen: wave (quarter, half); lane group g = lane >> 4 holds K slice 8g..8g+7
     const int quarter = wave >> 1, half = wave & 1;
@@ -1033,77 +1061,194 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     const uint4 *pq = g < 3 ? sQB + 48 * half * QT + lane : sZ + col;
     const uint4 *pa = g < 3 ? sA + lane : sZ + col;
     const int tstep = g < 3 ? 48 : 0;
-    pcm_bf16x8 bq[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) bq[qt] = __builtin_bit_cast(pcm_bf16x8, pq[qt * tstep]);
-    float best[QT], sec[QT];
+    float best[QT], sec[QT];  // (the wide form uses the first QTW of each)
     int bchunk[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) { best[qt] = PCM_INF; sec[qt] = PCM_INF; bchunk[qt] = 0; }
     const int ngroups = ntp >> 6;
-    // software-pipelined: each of the four A tiles (one ds_read_b128 each)
-    // is read for the wave's next group while the current group is screened
-    // (the wave's last group re-reads itself)
-    uint4 an[4];
-    // (lane group 3: the tile offset 48 i inside the zero region, no group step)
-    auto fetch = [&](int gi, int i) { an[i] = pa[4 * gi * tstep + 48 * i]; };
-    if (quarter < ngroups) {
+    // the wide form's lane roles: column (query of a 32-query tile, target row
+    // of a 32-row A tile) and K half
+    const int wh = lane >> 5, wc = lane & 31;
+    constexpr int QTW = QW / 2 / 32;  // 32-query tiles per wave
+    // (the wide loop has no register to spare: |q'|^2 crosses it, not q' --
+    // the empty asm keeps the compiler from sinking the sum behind the loop)
+    float qn2w = kWide ? __builtin_fmaf(qzc, qzc, __builtin_fmaf(qyc, qyc, qxc * qxc)) : 0.f;
+    if constexpr (kWide) asm volatile("" : "+v"(qn2w));
+    if constexpr (kWide) {
+        // ---- the wide screen (header: "The wide form").  Row p's slice j sits at
+        // uint4 48 (p >> 4) + 16 j + (p & 15).  The K-low operand of a 32-row
+        // tile is lane l's row wc, slice wh (K 8 wh..8 wh + 7).  The K-high
+        // MFMA carries slice 2 (K 16..23) in lanes 32-63 and the zero slots
+        // (K 24..31) in lanes 0-31: the queries' operand reads those from the
+        // zero region, once; the targets' one reads slice wh + 1 in every
+        // lane -- slice 1 in lanes 0-31, any finite values against those zeros
+        // -- so that a tile's two reads are one address and an immediate.  (A
+        // finite coordinate whose doubled bf16 part overflows would put
+        // inf x 0 = NaN there: its w is +inf too, R with it, and no screened
+        // value is trusted.)  Every 16-lane run of a read is 256 consecutive
+        // bytes.
+        const int r16 = 48 * (wc >> 4) + (wc & 15);
+        const uint4 *pql = sQB + 48 * (QW / 2 / 16) * half + r16 + 16 * wh;
+        const uint4 *pqh = wh ? sQB + 48 * (QW / 2 / 16) * half + r16 + 32 : sZ + wc;
+        const uint4 *pal = sA + r16 + 16 * wh;
+        const int hstep = wh ? 96 : 0;  // the query tiles' K-high step (none inside the zero region)
+        pcm_bf16x8 bl[QTW], bh[QTW];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) fetch(quarter, i);
-    }
-    // A group's 32 MFMAs (tile i = k / 8 against query tile k mod 8) are one
-    // sequence over kRot rotating result quads: MFMA k, then the two folds of
-    // MFMA k - kLag, whose result has landed by then, so no MFMA waits for a
-    // fold and no fold for its MFMA.  The sequence runs on across the groups:
-    // a group's last kLag results are folded behind the next group's first
-    // MFMAs (before the wave's first group the quads hold +inf), and the
-    // best/second/chunk update of the group before sits in the first eight
-    // gaps, behind those folds and ahead of each query tile's first fold of
-    // this group (mn = +inf before the first group: that update changes
-    // nothing).  The last group's folds and update follow the loop.  A query
-    // tile's folds stay in tile order 0..3.  Tile i is re-read in place for
-    // the next group right after its eight MFMAs: one read per eight MFMAs,
-    // no second buffer and no copy.  A fence behind every MFMA and behind its
-    // gap's folds pins this order (left to itself hipcc puts some folds ahead
-    // of their gap's MFMA, one instruction short of the result's latency).
-    constexpr int kRot = 4, kLag = 3;
-    float mn[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) mn[qt] = PCM_INF;
-    pcm_f4 d[kRot];
-#pragma unroll
-    for (int r = 0; r < kRot; ++r) d[r] = pcm_f4{PCM_INF, PCM_INF, PCM_INF, PCM_INF};
-    int cid = 0;  // chunk of the group whose mins mn holds
-    auto fold = [&](int k, bool first) {  // (a group's first fold of a query tile starts from +inf)
-        const pcm_f4 r = d[k % kRot];
-        mn[k % QT] = __builtin_fminf(__builtin_fminf(first ? PCM_INF : mn[k % QT], r.x), r.y);
-        mn[k % QT] = __builtin_fminf(__builtin_fminf(mn[k % QT], r.z), r.w);
-    };
-    auto update = [&](int qt) {
-        sec[qt] = __builtin_amdgcn_fmed3f(mn[qt], best[qt], sec[qt]);
-        if (mn[qt] < best[qt]) { best[qt] = mn[qt]; bchunk[qt] = cid; }
-    };
-    for (int gi = quarter; gi < ngroups; gi += 4) {
-        const int gn = gi + 4 < ngroups ? gi + 4 : gi;
-#pragma unroll
-        for (int k = 0; k < 4 * QT; ++k) {
-            d[k % kRot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pcm_bf16x8, an[k / QT]), bq[k % QT],
-                                                                  pcm_f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            if (k % QT == QT - 1) fetch(gn, k / QT);
-            __builtin_amdgcn_sched_barrier(0);
-            if (k < kLag) fold(4 * QT - kLag + k, false);
-            else fold(k - kLag, k - kLag < QT);
-            if (k < QT) update(k);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int qt = 0; qt < QTW; ++qt) {
+            bl[qt] = __builtin_bit_cast(pcm_bf16x8, pql[96 * qt]);
+            bh[qt] = __builtin_bit_cast(pcm_bf16x8, pqh[hstep * qt]);
         }
-        cid = 4 * gi + g;
+        // the group's two A tiles, K-low and K-high: four ds_read_b128 per
+        // group, each re-read in place for the wave's next group right after
+        // its last MFMA (the wave's last group re-reads itself)
+        uint4 al[2], ah[2];
+        auto fetch_lo = [&](int gi, int i) { al[i] = pal[192 * gi + 96 * i]; };
+        auto fetch_hi = [&](int gi, int i) { ah[i] = pal[192 * gi + 96 * i + 16]; };
+        if (quarter < ngroups) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) { fetch_lo(quarter, i); fetch_hi(quarter, i); }
+        }
+        // A group is eight pairs k = (A tile k / 4, query tile k mod 4) of
+        // chained MFMAs -- K 0..15 onto zero, K 16..31 onto that result in
+        // place -- over kAcc rotating 32 x 32 results.  Between pair k's two
+        // MFMAs stands the best/second/chunk update of pair k - 2, made with
+        // the minimum the fold before left: the second MFMA accumulates onto
+        // the first one's result and would otherwise wait it out with nothing
+        // of its wave to issue (back to back: 49 instead of 44 cycles per 256
+        // values).  Behind the second MFMA pair k - 1
+        // is folded (sixteen candidates of the lane's query, eight v_min3): a
+        // pair, an update and a fold later than its own MFMAs, so no fold waits
+        // for its result.  The sequence runs on across the groups: a group's
+        // last pair is folded and its last two updated behind the next group's
+        // first two (before the wave's first group the results and the minimum
+        // hold +inf: those updates change nothing), the wave's last behind the
+        // loop.  A query tile's updates stay in A-tile order.  The fences pin
+        // this order.
+        constexpr int kAcc = 2;
+        static_assert(8 % kAcc == 0, "the rotation runs on across the groups");
+        pcm_f16v acc[kAcc];
+#pragma unroll
+        for (int r = 0; r < kAcc; ++r)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[r][e] = PCM_INF;
+        float mnw = PCM_INF;  // the minimum of the pair folded last
+        // pair k (chunk cid of this lane) updated with mnw.  best is a
+        // minimum, not a select on the compare's mask: that mask is then read
+        // two instructions after the compare and needs no wait (a NaN mnw --
+        // sixteen overflowed w -- leaves best alone either way).  It is
+        // written as a v_min3 against +inf, like the fold's first: a
+        // two-operand minimum would first canonicalise its operands.
+        auto update = [&](int k, int cid) {
+            const int qt = k % QTW;
+            sec[qt] = __builtin_amdgcn_fmed3f(mnw, best[qt], sec[qt]);
+            bchunk[qt] = mnw < best[qt] ? cid : bchunk[qt];
+            best[qt] = __builtin_fminf(__builtin_fminf(PCM_INF, mnw), best[qt]);
+        };
+        auto fold = [&](int k) {  // pair k's sixteen candidates into mnw: eight v_min3
+            const pcm_f16v r = acc[k % kAcc];
+            mnw = __builtin_fminf(__builtin_fminf(PCM_INF, r[0]), r[1]);
+#pragma unroll
+            for (int e = 2; e < 16; e += 2) mnw = __builtin_fminf(__builtin_fminf(mnw, r[e]), r[e + 1]);
+        };
+        pcm_f16v zero16;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
+        int clast = 0;  // the group before: its last chunk of this lane
+        for (int gi = quarter; gi < ngroups; gi += 4) {
+            const int gn = gi + 4 < ngroups ? gi + 4 : gi;
+            const int cbase = 4 * gi + wh;
+#pragma unroll
+            for (int k = 0; k < 2 * QTW; ++k) {
+                acc[k % kAcc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pcm_bf16x8, al[k / QTW]),
+                                                                        bl[k % QTW], zero16, 0, 0, 0);
+                if (k % QTW == QTW - 1) fetch_lo(gn, k / QTW);
+                __builtin_amdgcn_sched_barrier(0);
+                if (k < 2) update(2 * QTW - 2 + k, clast);
+                else update(k - 2, cbase + 2 * ((k - 2) / QTW));
+                __builtin_amdgcn_sched_barrier(0);
+                acc[k % kAcc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pcm_bf16x8, ah[k / QTW]),
+                                                                        bh[k % QTW], acc[k % kAcc], 0, 0, 0);
+                if (k % QTW == QTW - 1) fetch_hi(gn, k / QTW);
+                __builtin_amdgcn_sched_barrier(0);
+                fold((k + 2 * QTW - 1) % (2 * QTW));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            clast = cbase + 2;
+        }
+        update(2 * QTW - 2, clast);
+        fold(2 * QTW - 1);
+        update(2 * QTW - 1, clast);
+    } else {
+        pcm_bf16x8 bq[QT];
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) bq[qt] = __builtin_bit_cast(pcm_bf16x8, pq[qt * tstep]);
+        // software-pipelined: each of the four A tiles (one ds_read_b128 each)
+        // is read for the wave's next group while the current group is screened
+        // (the wave's last group re-reads itself)
+        uint4 an[4];
+        // (lane group 3: the tile offset 48 i inside the zero region, no group step)
+        auto fetch = [&](int gi, int i) { an[i] = pa[4 * gi * tstep + 48 * i]; };
+        if (quarter < ngroups) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fetch(quarter, i);
+        }
+        // A group's 32 MFMAs (tile i = k / 8 against query tile k mod 8) are one
+        // sequence over kRot rotating result quads: MFMA k, then the two folds of
+        // MFMA k - kLag, whose result has landed by then, so no MFMA waits for a
+        // fold and no fold for its MFMA.  The sequence runs on across the groups:
+        // a group's last kLag results are folded behind the next group's first
+        // MFMAs (before the wave's first group the quads hold +inf), and the
+        // best/second/chunk update of the group before sits in the first eight
+        // gaps, behind those folds and ahead of each query tile's first fold of
+        // this group (mn = +inf before the first group: that update changes
+        // nothing).  The last group's folds and update follow the loop.  A query
+        // tile's folds stay in tile order 0..3.  Tile i is re-read in place for
+        // the next group right after its eight MFMAs: one read per eight MFMAs,
+        // no second buffer and no copy.  A fence behind every MFMA and behind its
+        // gap's folds pins this order (left to itself hipcc puts some folds ahead
+        // of their gap's MFMA, one instruction short of the result's latency).
+        constexpr int kRot = 4, kLag = 3;
+        float mn[QT];
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) mn[qt] = PCM_INF;
+        pcm_f4 d[kRot];
+#pragma unroll
+        for (int r = 0; r < kRot; ++r) d[r] = pcm_f4{PCM_INF, PCM_INF, PCM_INF, PCM_INF};
+        int cid = 0;  // chunk of the group whose mins mn holds
+        auto fold = [&](int k, bool first) {  // (a group's first fold of a query tile starts from +inf)
+            const pcm_f4 r = d[k % kRot];
+            mn[k % QT] = __builtin_fminf(__builtin_fminf(first ? PCM_INF : mn[k % QT], r.x), r.y);
+            mn[k % QT] = __builtin_fminf(__builtin_fminf(mn[k % QT], r.z), r.w);
+        };
+        auto update = [&](int qt) {
+            sec[qt] = __builtin_amdgcn_fmed3f(mn[qt], best[qt], sec[qt]);
+            if (mn[qt] < best[qt]) { best[qt] = mn[qt]; bchunk[qt] = cid; }
+        };
+        for (int gi = quarter; gi < ngroups; gi += 4) {
+            const int gn = gi + 4 < ngroups ? gi + 4 : gi;
+#pragma unroll
+            for (int k = 0; k < 4 * QT; ++k) {
+                d[k % kRot] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    __builtin_bit_cast(pcm_bf16x8, an[k / QT]), bq[k % QT], pcm_f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                if (k % QT == QT - 1) fetch(gn, k / QT);
+                __builtin_amdgcn_sched_barrier(0);
+                if (k < kLag) fold(4 * QT - kLag + k, false);
+                else fold(k - kLag, k - kLag < QT);
+                if (k < QT) update(k);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            cid = 4 * gi + g;
+        }
+#pragma unroll
+        for (int k = 4 * QT - kLag; k < 4 * QT; ++k) fold(k, false);
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) update(qt);
     }
-#pragma unroll
-    for (int k = 4 * QT - kLag; k < 4 * QT; ++k) fold(k, false);
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) update(qt);
     __syncthreads();  // every wave is done reading sA / sQB
     PCM_STAMP(3);
+#ifdef PCM_STAMPS
+    if (tid == 0 && blockIdx.x < 4096) g_pcm_stamps[(8192 + blockIdx.x) * 8 + 3] = __builtin_amdgcn_s_memtime();
+#endif
     // raw tile for the rescans (this thread's staged targets)
 #pragma unroll
     for (int r = 0; r < kPer; ++r) {
@@ -1119,16 +1264,33 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     // partials of tiles 4 (g >> 1) + 2 (g & 1) + {0, 1}; one partial per
     // (quarter, query) to LDS
     static_assert(QT == 8, "two halving steps: 8 query tiles -> 2 per lane");
+    if constexpr (kWide) {
+        // the wide form: the two lane halves hold the same 4 query tiles
+        // against different chunks; one step leaves lane half wh with the
+        // folded partials of tiles 2 wh + {0, 1}
+        static_assert(QTW == 4, "one halving step: 4 query tiles -> 2 per lane");
+        int t2;  // (a copy of tid the compiler cannot see through: wc is recomputed, not carried across the loop)
+        asm volatile("v_mov_b32 %0, %1" : "=v"(t2) : "v"(tid));
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-        mfma_fold_step<true>(best[j], sec[j], bchunk[j], best[j + 4], sec[j + 4], bchunk[j + 4]);
+        for (int j = 0; j < 2; ++j) {
+            mfma_fold_step<true>(best[j], sec[j], bchunk[j], best[j + 2], sec[j + 2], bchunk[j + 2]);
+            const int s = half * (QW / 2) + (2 * ((t2 >> 5) & 1) + j) * 32 + (t2 & 31);
+            sPB[quarter][s] = best[j];
+            sPS[quarter][s] = sec[j];
+            sPC[quarter][s] = bchunk[j];
+        }
+    } else {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        mfma_fold_step<false>(best[j], sec[j], bchunk[j], best[j + 2], sec[j + 2], bchunk[j + 2]);
-        const int s = half * (QW / 2) + (4 * (g >> 1) + 2 * (g & 1) + j) * 16 + col;
-        sPB[quarter][s] = best[j];
-        sPS[quarter][s] = sec[j];
-        sPC[quarter][s] = bchunk[j];
+        for (int j = 0; j < 4; ++j)
+            mfma_fold_step<true>(best[j], sec[j], bchunk[j], best[j + 4], sec[j + 4], bchunk[j + 4]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            mfma_fold_step<false>(best[j], sec[j], bchunk[j], best[j + 2], sec[j + 2], bchunk[j + 2]);
+            const int s = half * (QW / 2) + (4 * (g >> 1) + 2 * (g & 1) + j) * 16 + col;
+            sPB[quarter][s] = best[j];
+            sPS[quarter][s] = sec[j];
+            sPC[quarter][s] = bchunk[j];
+        }
     }
     const int any_nonfinite = pcm_wg_or(nonfinite, sNFm, W);
     PCM_STAMP(4);
@@ -1172,7 +1334,7 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
             // every target that can reach the best chunk's exact minimum d_b
             // <= fb + |q'|^2 + eR: E <= 80u (2|q'| + sqrt(db))^2
             const float kAbs = 7.888609052210118e-31f;  // 2^-100
-            const float qn2 = __builtin_fmaf(qzc, qzc, __builtin_fmaf(qyc, qyc, qxc * qxc));
+            const float qn2 = kWide ? qn2w : __builtin_fmaf(qzc, qzc, __builtin_fmaf(qyc, qyc, qxc * qxc));
             const float sq = __builtin_amdgcn_sqrtf(qn2);
             const float rr = __builtin_amdgcn_sqrtf(rmax2) + sq;
             const float eR = kFiltU80 * (rr * rr) * 1.001f + kAbs;
@@ -1187,18 +1349,23 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
                     // two quads of the raw tile, 16 targets apart; a quad stays
                     // contiguous under mslot, and slots past nt (inside the last
                     // 64-target group) hold stale bytes that `take` ignores
-                    const int k0 = 64 * (fc >> 2) + 32 * part + 4 * (fc & 3);
+                    // (the wide form's chunk: A tile (fc >> 1) & 1 of the group,
+                    // lane half fc & 1 -- rows 8 j + 4 (fc & 1) + r, j = 2 part,
+                    // 2 part + 1: two quads 8 targets apart)
+                    constexpr int kQuad = kWide ? 8 : 16;
+                    const int k0 = kWide ? 64 * (fc >> 2) + 32 * ((fc >> 1) & 1) + 4 * (fc & 1) + 16 * part
+                                         : 64 * (fc >> 2) + 32 * part + 4 * (fc & 3);
                     pcm_f4 tx[2], ty[2], tz[2];
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const int o = mslot(k0 + 16 * h);
+                        const int o = mslot(k0 + kQuad * h);
                         tx[h] = *reinterpret_cast<const pcm_f4 *>(&sT[0][o]);
                         ty[h] = *reinterpret_cast<const pcm_f4 *>(&sT[1][o]);
                         tz[h] = *reinterpret_cast<const pcm_f4 *>(&sT[2][o]);
                     }
 #pragma unroll
                     for (int k = 0; k < 8; ++k) {  // ascending: strict '<' keeps the lowest
-                        const int kk = k0 + 16 * (k >> 2) + (k & 3);
+                        const int kk = k0 + kQuad * (k >> 2) + (k & 3);
                         const float d = pcm_sqd(tx[k >> 2][k & 3] - qx, ty[k >> 2][k & 3] - qy, tz[k >> 2][k & 3] - qz);
                         const bool take = (d < hd) & (kk < nt);
                         hd = take ? d : hd;
@@ -1237,7 +1404,8 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
             int bk = 0x7fffffff;
             {
                 const int pc = sPC[g][sq];
-                const int k = 64 * (pc >> 2) + 16 * (col >> 2) + 4 * (pc & 3) + (col & 3);
+                const int k = kWide ? 64 * (pc >> 2) + 32 * ((pc >> 1) & 1) + 4 * (pc & 1) + 8 * (col >> 2) + (col & 3)
+                                    : 64 * (pc >> 2) + 16 * (col >> 2) + 4 * (pc & 3) + (col & 3);
                 const bool on = ((plan >> (4 + g)) & 1u) && k < nt;
                 const int ks = mslot(min(k, nt - 1));
                 const float d = pcm_sqd(sT[0][ks] - x, sT[1][ks] - y, sT[2][ks] - z);
@@ -2132,7 +2300,7 @@ __device__ __forceinline__ void poll_grad_loss_wg(int b, int n, int m, int per, 
 // (pcm_chamfer_loss_grad_rescale checks it against the real one).
 template <int W, int QPT, int C, int TILE, bool kMfma = false, bool kGran = false, bool kEarly = false,
           bool kLocal = false, bool kSplit = false, bool kG4 = false, bool kG4x = false, int LAY1 = 0, int LAY2 = 0,
-          bool kLayOne = false, bool kOwnK = false>
+          bool kLayOne = false, bool kOwnK = false, bool kWide = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) void chamfer_loss_grad_kernel(
     const float *__restrict__ xyz1, const float *__restrict__ xyz2, int b, int n, int m, float w1, float w2,
     float *__restrict__ dist1, float *__restrict__ dist2, int32_t *__restrict__ idx1, int32_t *__restrict__ idx2,
@@ -2145,6 +2313,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
     constexpr int QW = 64 * QPT;
     constexpr int NT = 64 * W;
     static_assert(!kMfma || (W == 8 && QPT == 4 && TILE == kMfmaTile), "the MFMA forward's fixed geometry");
+    static_assert(!kWide || kMfma, "the wide screen loop: a form of the MFMA forward");
     constexpr int kFwd = kMfma ? MfmaLds::kBytes : FiltLds<W, QPT, TILE>::kBytes;
     static_assert(!kMfma || kFwd <= kGradBytes,
                   "two workgroups' LDS per CU: the polling workgroup runs beside the forward workgroups from the start");
@@ -2172,6 +2341,11 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
         gsc = *gscale;
         w1 = __fmul_rn(gsc, w1);
         w2 = __fmul_rn(gsc, w2);
+    }
+    if constexpr (kWide) {
+        // uniform: scalar registers carry them across the forward (the wide loop has no vector one to spare)
+        w1 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(w1)));
+        w2 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(w2)));
     }
     if ((int)blockIdx.x == nprod) {
         PCM_STAMP2(5);
@@ -2216,11 +2390,11 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
         float my_d;
         if constexpr (kMfma) {
             // one inlined forward: the layouts reach its prologue loads only
-            my_d = filt_forward_mfma<false>(first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
-                                            first ? dist1 + (size_t)batch * n : dist2 + (size_t)batch * m,
-                                            first ? idx1 + (size_t)batch * n : idx2 + (size_t)batch * m, arena,
-                                            first ? G1 : G2, tag, first ? L1 : L2, first ? L2 : L1,
-                                            kOwnK ? &myk : nullptr);
+            my_d = filt_forward_mfma<false, kWide>(
+                first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
+                first ? dist1 + (size_t)batch * n : dist2 + (size_t)batch * m,
+                first ? idx1 + (size_t)batch * n : idx2 + (size_t)batch * m, arena, first ? G1 : G2, tag,
+                first ? L1 : L2, first ? L2 : L1, kOwnK ? &myk : nullptr);
         } else if constexpr (LAY1 == LAY2) {
             const PcmLay LQ = LAY1 ? PcmLay{1, first ? n : m} : PcmLay{3, 1};
             my_d = filt_forward<float, W, QPT, C, TILE, false, kSplit>(
@@ -2319,9 +2493,9 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
     }
     float my_d;
     if constexpr (kMfma)
-        my_d = filt_forward_mfma<true>(first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
-                                       first ? dist1 + (size_t)batch * n : dist2 + (size_t)batch * m,
-                                       first ? idx1 + (size_t)batch * n : idx2 + (size_t)batch * m, arena);
+        my_d = filt_forward_mfma<true, kWide>(first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
+                                              first ? dist1 + (size_t)batch * n : dist2 + (size_t)batch * m,
+                                              first ? idx1 + (size_t)batch * n : idx2 + (size_t)batch * m, arena);
     else
         my_d = filt_forward<float, W, QPT, C, TILE, true>(
             first ? X1 : X2, first ? X2 : X1, first ? n : m, first ? m : n, q0,
@@ -2510,8 +2684,13 @@ struct GradVariant {
 // matrix-core screen (filt_forward_mfma), for every size the entry takes
 // (n, m <= 1024): 12.4 against 13.65 us in tools/ab_chamfer.py, the bench's
 // own figures in DESIGN.md section 3.5c (profiles/mfma_screen/).
-constexpr int kDefaultGradVariant = 19;
-#define PCM_GRAD_DEFAULT(L1, L2) chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, L1, L2>
+// Then variant 20, 19 with the wide screen loop (chained 32x32x16 MFMA pairs,
+// filt_forward_mfma<.., true>): 11.2 against 11.7 us in tools/ab_chamfer.py
+// (profiles/wide_screen/).
+constexpr int kDefaultGradVariant = 20;
+#define PCM_GRAD_DEFAULT_FORM(L1, L2, ONE) \
+    chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, L1, L2, ONE, false, true>
+#define PCM_GRAD_DEFAULT(L1, L2) PCM_GRAD_DEFAULT_FORM(L1, L2, false)
 // The product library holds the default only; the measured alternatives are
 // compiled into the tuning build (make tune: -DPCM_TUNE, libpcm_hip_tune.so),
 // which tools/ and the variant tests load.
@@ -2552,8 +2731,10 @@ const GradVariant kGradVariants[] = {
     // 18: 7 with the range's own argmins from its forward (8-byte granules, no
     // own-range granule reads)
     {18, chamfer_loss_grad_kernel<8, 4, 16, 1024, false, true, false, false, false, false, false, 0, 0, false, true>, 8, 4},
+    // 19: 7's hand-off and gradient phase behind the matrix-core screen (filt_forward_mfma); the default until 20
+    {19, chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true>, 8, 4},
 #endif
-    // 19 (the default): 7's hand-off and gradient phase behind the matrix-core screen (filt_forward_mfma)
+    // 20 (the default): 19 with the wide screen loop (chained 32x32x16 MFMA pairs, filt_forward_mfma<.., true>)
     {kDefaultGradVariant, PCM_GRAD_DEFAULT(0, 0), 8, 4},
 };
 // the default variant with cloud 1 / cloud 2 in channel planes (index 2 lay1 + lay2)
@@ -2565,11 +2746,12 @@ const grad_kernel_t kGradDefaultLay[4] = {PCM_GRAD_DEFAULT(0, 0), PCM_GRAD_DEFAU
 // in it and the instances stay only so that lay_form 1 keeps its meaning
 const grad_kernel_t kGradLayOne[4] = {
     PCM_GRAD_DEFAULT(0, 0),
-    chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, 0, 1, true>,
-    chamfer_loss_grad_kernel<8, 4, 16, 1024, true, true, false, false, false, false, false, 1, 0, true>,
+    PCM_GRAD_DEFAULT_FORM(0, 1, true),
+    PCM_GRAD_DEFAULT_FORM(1, 0, true),
     PCM_GRAD_DEFAULT(1, 1)};
 #endif
 #undef PCM_GRAD_DEFAULT
+#undef PCM_GRAD_DEFAULT_FORM
 // (round 5, rejected: 15 with two queries per lane -- 128-query workgroups,
 // two per CU, four waves per SIMD -- 15.45 us against 13.39 us,
 // profiles/r05/ab_qpt2_r05t.txt)
@@ -2579,7 +2761,7 @@ const grad_kernel_t kGradLayOne[4] = {
 // their own while staging, one barrier after the scan instead of two -- 13.28
 // against 13.16 us, profiles/r04/chamfer_sept_r04q_ab.txt)
 constexpr int kNumGradVariants = sizeof(kGradVariants) / sizeof(kGradVariants[0]);
-constexpr int kMaxTuneVariantId = 19;  // the highest id of the tuning build's table above
+constexpr int kMaxTuneVariantId = 20;  // the highest id of the tuning build's table above
 // tools/tune_chamfer.py (profiles/r01): B=32, N=M=1024 -- W=8 QPT=4 18.7 us,
 // W=8 QPT=2 19.3 us, W=4 QPT=2 21.4 us; round 2: variant 1 (arrival counter
 // hand-off) 16.25 us, variant 7 (the same forward, granule hand-off) 14.97 us
@@ -2614,7 +2796,7 @@ long long grad_blocks_max(int b, int n, int m) {
 }
 
 // the matrix-core forward takes single-tile clouds (n, m <= kMfmaTile): that is
-// the entry's own limit (kGradCap, checked by launch_loss_grad), so 19 serves
+// the entry's own limit (kGradCap, checked by launch_loss_grad), so 20 serves
 // every size the entry accepts
 static_assert(kMfmaTile >= kGradCap, "the default serves every size the entry takes");
 int default_grad_variant(int, int, int) { return kDefaultGradVariant; }

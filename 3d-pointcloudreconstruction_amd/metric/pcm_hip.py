@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get(
     "PCM_HIP_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libpcm_hip.so"))
 # the tuning build (make -C csrc tune): the product library plus the measured
-# alternatives of the one-launch Chamfer step (fused variants 0-18 beside the default 19), which
+# alternatives of the one-launch Chamfer step (fused variants 0-19 beside the default 20), which
 # tools/ and the variant tests select by number; never on the product path
 TUNE_LIB_PATH = os.environ.get(
     "PCM_HIP_TUNE_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libpcm_hip_tune.so"))
@@ -68,7 +68,7 @@ def load_library():
 
 
 def load_tune_library():
-    """Load libpcm_hip_tune.so, the tuning build (fused variants 0-18 beside
+    """Load libpcm_hip_tune.so, the tuning build (fused variants 0-19 beside
     the default); raises OSError if it is missing."""
     global _tune_lib
     if _tune_lib is None:
@@ -728,7 +728,7 @@ def tune_num_chamfer_loss_grad_variants() -> int:
 
 
 # the product library's one-launch step (csrc/chamfer_filt.hip kDefaultGradVariant)
-DEFAULT_LOSS_GRAD_VARIANT = 19
+DEFAULT_LOSS_GRAD_VARIANT = 20
 
 
 def mean_weight(count: int) -> float:

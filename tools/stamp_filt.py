@@ -131,7 +131,7 @@ def run_fused(v, b, n, m, dev):
           f"{statistics.median(spread):.2f} max {max(spread):.2f} us")
     # the forward's own stamps (table's lower half, same workgroup numbering)
     lo = [[buf[i * 8 + k] for k in range(8)] for i in range(nblk - 1)]
-    if v in (6, 19):  # the matrix-core forward stores its near-tie census in slot 0
+    if v in (6, 19, 20):  # the matrix-core forward stores its near-tie census in slot 0
         nl = [r[0] & 0xffff for r in lo]
         full = sum((r[0] >> 16) & 0xffffff for r in lo)
         single = sum(r[0] >> 40 for r in lo)
@@ -142,6 +142,12 @@ def run_fused(v, b, n, m, dev):
         ghz = [(c[6] - c[1]) / ((r[6] - r[1]) * 10.0) for c, r in zip(cyc, lo) if r[6] > r[1]]
         print(f"  shader clock over stamps 1..6: median {statistics.median(ghz):.2f} GHz, "
               f"min {min(ghz):.2f}, max {max(ghz):.2f}")
+        # the scan in shader cycles (s_memtime at stamps 2 and 3): a wave screens
+        # 4 groups of 64 targets x 128 queries, 128 quads of 256 values
+        scan = [c[3] - c[2] for c in cyc if c[3] > c[2]]
+        if scan:
+            print(f"  scan: median {statistics.median(scan):.0f} shader cycles = "
+                  f"{statistics.median(scan) / 128.0:.1f} per 256 screened values per wave")
         for r in lo:
             r[0] = r[1]
     else:
@@ -157,7 +163,7 @@ def run_fused(v, b, n, m, dev):
               f"max {max(dur):7.2f}  (>1 us: {sum(d > 1.0 for d in dur)} workgroups)")
 
 
-FUSED_QPT = [2, 4, 2] + [4] * 17                                   # csrc/chamfer_filt.hip kGradVariants
+FUSED_QPT = [2, 4, 2] + [4] * 18                                   # csrc/chamfer_filt.hip kGradVariants
 
 
 def main():
