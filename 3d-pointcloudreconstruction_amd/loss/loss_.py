@@ -3,8 +3,9 @@
 Same function names and signatures (loss/loss_.py:9-13, :79-109, :122-140):
 ``cd``, ``distChamfer``, ``batch_NN_loss`` and ``fscore``.  The reference
 resolves ``dist_chamfer_3D`` relative to the working directory (:6); here it
-is resolved relative to this file.  Left out: ``batch_EMD_loss`` (:111-120),
-which needs the third-party geomloss package.
+is resolved relative to this file.  ``batch_EMD_loss`` (:111-120), which the
+reference builds on the third-party geomloss package, lives in
+loss/kernel_loss.py with the kernel norms it needs.
 
 Differences:
   * ``distChamfer`` / ``batch_NN_loss`` build no B x N x M float64 matrix

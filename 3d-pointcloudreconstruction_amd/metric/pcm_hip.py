@@ -42,6 +42,7 @@ EXPORTED = (
     "pcm_fps",
     "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
     "pcm_ball_query", "pcm_uniform_workspace_bytes", "pcm_uniform_loss",
+    "pcm_kernel_loss_workspace_bytes", "pcm_kernel_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -214,6 +215,11 @@ def _open(path):
         L.pcm_uniform_workspace_bytes.argtypes = [ci, ci, ci, ci, vp]
         L.pcm_uniform_loss.restype = ci
         L.pcm_uniform_loss.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, ctypes.c_double, vp, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_kernel_loss"):  # absent from A/B builds of older sources
+        L.pcm_kernel_loss_workspace_bytes.restype = cs
+        L.pcm_kernel_loss_workspace_bytes.argtypes = [ci, ci, ci]
+        L.pcm_kernel_loss.restype = ci
+        L.pcm_kernel_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1140,6 +1146,62 @@ def uniform_loss(xyz, lay, npoint, nsample, ball_radius, weight, expect_len, los
                                                radii, weights, float(expect_len), _ptr(loss_out), _ptr(gradxyz),
                                                _ptr(groups), _ptr(workspace), workspace.numel(), _stream(dev)),
                "pcm_uniform_loss")
+
+
+KERNEL_GAUSSIAN, KERNEL_LAPLACIAN, KERNEL_ENERGY = 0, 1, 2  # include/pcm.h PCM_KERNEL_*
+KERNEL_LOSS_MAX_POINTS = 16384  # include/pcm.h PCM_KERNEL_LOSS_MAX_POINTS
+KERNEL_LOSS_ROWS = 128  # row points per workgroup of csrc/kernel_loss.hip (kKlRows: two to a lane)
+KERNEL_LOSS_TILE = 1024  # column points per LDS tile of csrc/kernel_loss.hip (kKlTile), an eighth to a wave
+KERNEL_LOSS_WAVES = 8  # waves that share a tile (kKlWaves)
+
+
+def kernel_loss_chain(n: int, m: int) -> int:
+    """The longest chain of float32 additions behind a row sum of
+    pcm_kernel_loss (include/pcm.h): wave 0's share of the larger cloud plus
+    the additions that merge the waves."""
+    share = KERNEL_LOSS_TILE // KERNEL_LOSS_WAVES
+    return max(share * (c // KERNEL_LOSS_TILE) + min(share, c % KERNEL_LOSS_TILE) + KERNEL_LOSS_WAVES - 1
+               for c in (int(n), int(m)))
+
+
+def kernel_loss_workspace(dev: torch.device, b: int, n: int, m: int) -> torch.Tensor:
+    """Scratch for kernel_loss (two float32 sums per point): ONE buffer per
+    (device, current stream), grown when a larger problem needs more; its
+    content on entry is irrelevant and it holds nothing between calls."""
+    need = max(int(load_library().pcm_kernel_loss_workspace_bytes(b, n, m)), 8)
+    key = ("kernel_loss", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def kernel_loss(xyz1, lay1, xyz2, lay2, kernel, blur, loss_out, gradxyz1=None, gradxyz2=None, workspace=None) -> None:
+    """pcm_kernel_loss on the float32 clouds xyz1 [B, N, 3] and xyz2 [B, M, 3]
+    (each rows, or a view of channel planes: layout 1): loss_out [B] = the
+    kernel norm 1/2 |alpha - beta|^2_k of the two uniformly weighted clouds of
+    every element for kernel KERNEL_GAUSSIAN / _LAPLACIAN / _ENERGY at `blur`;
+    gradxyz1 / gradxyz2 (each optional; its cloud's shape and layout) = the
+    gradient of loss_out[bi] in that cloud."""
+    tensors = (xyz1, xyz2, loss_out) + tuple(t for t in (gradxyz1, gradxyz2) if t is not None)
+    dev = _require_device(*tensors)
+    _knn_cloud(xyz1, lay1, "kernel_loss")
+    _knn_cloud(xyz2, lay2, "kernel_loss")
+    b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    if xyz2.shape[0] != b:
+        raise ValueError("kernel_loss takes clouds of one batch size")
+    if loss_out.dtype != torch.float32 or tuple(loss_out.shape) != (b,) or not loss_out.is_contiguous():
+        raise ValueError(f"loss_out must be contiguous float32 of shape {(b,)}")
+    for g, x, lay in ((gradxyz1, xyz1, lay1), (gradxyz2, xyz2, lay2)):
+        if g is not None and (g.dtype != torch.float32 or g.shape != x.shape or cloud_layout(g) != int(lay)):
+            raise ValueError("a gradient must have its cloud's dtype, shape and layout")
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = kernel_loss_workspace(dev, b, n, m)
+        _check(load_library().pcm_kernel_loss(_ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), int(kernel),
+                                              float(blur), _ptr(loss_out), _ptr(gradxyz1), _ptr(gradxyz2),
+                                              _ptr(workspace), workspace.numel(), _stream(dev)), "pcm_kernel_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:
