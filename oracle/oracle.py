@@ -6,8 +6,12 @@ and ``bench.py``'s ``cpu_baseline`` leg may import this module, and only as the
 checker / the timed CPU baseline -- never as the product path.
 
 Parity status: Chamfer pinned by tests/golden (reference utils/utils.py:246-290);
-EMD partially pinned (reference invariant metric/emd/test.py:24-28 only; the rest
-is "parity unpinned" beyond this deterministic restatement).
+EMD pinned by the reference invariant (metric/emd/test.py:24-28).  Both are also
+pinned in STRUCTURE (tiles, tie order, GetMax window, NaN rules, backward add
+order) against a host build of the reference's own kernels (ref_build.py,
+tests/test_oracle_reference_cpu.py), EMD under the lowest-index schedule.  What
+stays "parity unpinned" is nvcc's FMA contraction of x*x+y*y+z*z: that build is
+unfused (order=1 here), the default order=0 is the pattern attributed to nvcc.
 """
 from __future__ import annotations
 
@@ -47,6 +51,7 @@ def lib():
                                                   _i32p, _i32p, _f32p, _f32p, c_int]
         L.pcm_oracle_emd_forward.argtypes = [_f32p, _f32p, c_int, c_int, c_float, c_int,
                                              _f32p, _i32p, ctypes.c_void_p, ctypes.c_void_p, c_int]
+        L.pcm_oracle_emd_forward_order.argtypes = L.pcm_oracle_emd_forward.argtypes + [c_int]
         L.pcm_oracle_emd_backward.argtypes = [_f32p, _f32p, c_int, c_int, _f32p, _i32p, _f32p]
         L.pcm_oracle_emd_values.argtypes = [_f32p, _f32p, _f32p, c_int, _f32p]
         L.pcm_oracle_emd_bid.argtypes = [_f32p, _f32p, _f32p, c_int, c_int, _i32p, _f32p, _f32p]
@@ -55,7 +60,7 @@ def lib():
         L.pcm_oracle_num_threads.restype = c_int
         for name in ("pcm_oracle_chamfer_nn", "pcm_oracle_chamfer_forward",
                      "pcm_oracle_chamfer_backward", "pcm_oracle_emd_forward",
-                     "pcm_oracle_emd_backward"):
+                     "pcm_oracle_emd_forward_order", "pcm_oracle_emd_backward"):
             getattr(L, name).restype = None
         _lib = L
     return _lib
@@ -109,9 +114,12 @@ def chamfer_backward(xyz1, xyz2, graddist1, graddist2, idx1, idx2, nthreads: int
     return g1, g2
 
 
-def emd_forward(xyz1, xyz2, eps: float, iters: int, with_stats: bool = False, nthreads: int = 0):
+def emd_forward(xyz1, xyz2, eps: float, iters: int, with_stats: bool = False, nthreads: int = 0,
+                order: int = 0):
     """emd_cuda_forward (emd_cuda.cu:228-282), deterministic tie rule.
 
+    order selects the squared-distance evaluation in the bid value and the
+    final dist, as in chamfer_nn (0 = pinned FMA order, 1 = unfused).
     Returns (dist, assignment) or, with_stats, (dist, assignment, price, unass_hist)."""
     xyz1, xyz2 = _f32(xyz1), _f32(xyz2)
     b, n, _ = xyz1.shape
@@ -119,9 +127,9 @@ def emd_forward(xyz1, xyz2, eps: float, iters: int, with_stats: bool = False, nt
     ass = np.zeros((b, n), np.int32)
     price = np.zeros((b, n), np.float32)
     hist = np.zeros(max(iters, 1), np.int64)
-    lib().pcm_oracle_emd_forward(xyz1, xyz2, b, n, float(eps), int(iters), dist, ass,
-                                 price.ctypes.data, hist.ctypes.data if with_stats else None,
-                                 nthreads)
+    lib().pcm_oracle_emd_forward_order(xyz1, xyz2, b, n, float(eps), int(iters), dist, ass,
+                                       price.ctypes.data, hist.ctypes.data if with_stats else None,
+                                       nthreads, int(order))
     if with_stats:
         return dist, ass, price, hist[:iters]
     return dist, ass
