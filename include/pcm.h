@@ -751,6 +751,15 @@ size_t pcm_emd_workspace_bytes(int b, int n);
  * bytes; its content on entry is irrelevant; calls that share a workspace must
  * be stream-ordered.  `price` may be NULL; otherwise it receives the final
  * object prices [b, n] (diagnostics / parity tests).
+ * Input contract: any finite coordinates for which every pairwise squared
+ * distance is finite in float32 (not only the reference's [0, 1]); eps >= 0,
+ * which the proofs behind the kernel's pruning need (prices must never fall).
+ * There assignment, dist and price equal the CPU oracle's bit for bit
+ * (tests/test_emd_stress_gpu.py: scales 1e-4 to 1e5, offsets, planar,
+ * collinear, lattice, coincident, collapsed and bimodal clouds).  Non-finite
+ * coordinates, or magnitudes at which a squared distance overflows to
+ * infinity (coordinates apart by more than about 1e19), are outside it and
+ * untested.
  */
 int pcm_emd_forward(const float *xyz1, const float *xyz2, int b, int n, float eps, int iters,
                     float *dist, int32_t *assignment, float *price,

@@ -35,7 +35,8 @@ import ref_build  # noqa: E402
 import reference_cases as C  # noqa: E402
 
 OUT = os.path.join(HERE, "ref_kernels_golden.npz")
-EMD_RECORDED = ("b2_n1024_eps005", "converged_n1024", "exact_ties_n4096")
+EMD_RECORDED = ("b2_n1024_eps005", "converged_n1024", "exact_ties_n4096",
+                "scale_1e-4", "scale_1e3", "small_scale_big_eps")
 EMD_BACKWARD = "b2_n1024_eps005"
 CHAMFER_RECORDED = ("nan_tiles_700x1300", "nan_tile3_300x1600", "finite_500x900")
 CHAMFER_BACKWARD = "finite_500x900"

@@ -7,6 +7,8 @@ Everything is seeded numpy, so both see the same bits.
 """
 import numpy as np
 
+import emd_stress_cases as S
+
 
 def uniform_clouds(seed, b, n):
     g = np.random.default_rng(seed)
@@ -61,6 +63,15 @@ EMD_CASES = {
     "converged_n1024": (lambda: uniform_clouds(7, 1, 1024), 0.1, 260, True, True),
     "n3072": (lambda: uniform_clouds(3, 1, 3072), 0.05, 100, False, False),
     "exact_ties_n4096": (lambda: exact_tie_clouds(40, 1, 4096), 0.05, 60, False, False),
+    # the oracle's double-precision GetMax window and its -1e9 start values away
+    # from the unit cube (tests/emd_stress_cases.py, n = 1024).  Increments of
+    # the two small-scale cases fall inside the 1e-6 window, where the schedule
+    # picks the claimant: racy in the reference.  Values near -1e3 do not.
+    "scale_1e-4": (lambda: S.clouds("scale_1e-4", 1024)[:2], S.CASES["scale_1e-4"][1], 60, False, False),
+    "scale_1e3": (lambda: S.clouds("scale_1e3", 1024)[:2], S.CASES["scale_1e3"][1], 60, True, False),
+    # no bidder from iteration 14 on
+    "small_scale_big_eps": (lambda: S.clouds("small_scale_big_eps", 1024)[:2], S.CASES["small_scale_big_eps"][1],
+                            40, False, True),
 }
 
 # name -> clouds.  The 512-point tile rules (chamfer3D.cu:36,79,121,126): a NaN

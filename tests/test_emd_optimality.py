@@ -23,10 +23,10 @@ per cloud bidding at the last iteration (oracle, seed 5: 4 bidders left from
 iteration 8,113 on), so its result is not a bijection -- the reference's own
 caveat; that setting is pinned bit-exact against the oracle in test_emd_gpu.py.
 """
-import numpy as np
 import pytest
 import torch
-from scipy.optimize import linear_sum_assignment
+
+from emd_optimality_check import check_eps_optimal
 
 # float32 values and prices (magnitude < 8): a few ulps of slack on top of eps
 SLACK = 1e-5
@@ -40,20 +40,7 @@ def _clouds(seed, b, n):
 def _check_eps_optimal(x1, x2, ass, price, eps):
     """One batch element: bijection, eps-CS at the final prices, and
     OPT <= cost <= OPT + n * eps.  Returns (cost - OPT) / (n * eps)."""
-    n = x1.shape[0]
-    np.testing.assert_array_equal(np.sort(ass), np.arange(n))  # converged: a bijection
-    dif = x1[:, None, :].astype(np.float64) - x2[None, :, :].astype(np.float64)
-    dist = np.sqrt((dif * dif).sum(-1))
-    val = (3.0 - dist) - price.astype(np.float64)[None, :]
-    rows = np.arange(n)
-    gap = val.max(1) - val[rows, ass]
-    assert gap.max() <= eps + SLACK, f"eps-CS broken: worst gap {gap.max()} > eps {eps}"
-    cost = dist[rows, ass].sum()
-    r, c = linear_sum_assignment(dist)
-    opt = dist[r, c].sum()
-    assert cost >= opt - 1e-9 * n
-    assert cost <= opt + n * (eps + SLACK), f"cost {cost} above OPT {opt} + n*eps {n * eps}"
-    return (cost - opt) / (n * eps)
+    return check_eps_optimal(x1, x2, ass, price, eps, slack=SLACK).excess
 
 
 @pytest.mark.parametrize("b,n,eps,iters,seed", [
