@@ -13,7 +13,8 @@ autograd Function (csrc/kernel_loss.hip; include/pcm.h has the contract):
 differentiable in both clouds, defined for any N and M (N != M included), with
 no assignment or argmin in it.  ``loss='gaussian'`` is not a Sinkhorn
 divergence and, despite the reference's name for it, not an earth mover's
-distance; ``loss='sinkhorn'`` is not offered.
+distance; ``loss='sinkhorn'`` is not offered by this module: loss/sinkhorn_loss.py has
+it (and delegates the kernel norms here).
 
 geomloss is not installed where this module was written and could not be
 fetched: the formulas are its published ones and are not verified against the
@@ -97,13 +98,13 @@ class SamplesLoss(nn.Module):
     p, blur)(x, y)`` with x [N, 3] and y [M, 3] gives a scalar, with x
     [B, N, 3] and y [B, M, 3] one value per batch element.  ``loss`` is
     'gaussian', 'laplacian' or 'energy'; ``p`` is accepted and not used (it
-    belongs to 'sinkhorn')."""
+    belongs to 'sinkhorn', which loss/sinkhorn_loss.py's SamplesLoss offers)."""
 
     def __init__(self, loss="gaussian", p=2, blur=0.05, **kwargs):
         super().__init__()
         if loss not in KERNELS:
             raise NotImplementedError(f"SamplesLoss(loss={loss!r}) is not offered here: the kernel norms "
-                                      f"{sorted(KERNELS)} are")
+                                      f"{sorted(KERNELS)} are (loss/sinkhorn_loss.py has 'sinkhorn')")
         if kwargs:
             raise NotImplementedError(f"SamplesLoss options {sorted(kwargs)} are not offered here")
         if not float(blur) > 0:

@@ -43,6 +43,7 @@ EXPORTED = (
     "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
     "pcm_ball_query", "pcm_uniform_workspace_bytes", "pcm_uniform_loss",
     "pcm_kernel_loss_workspace_bytes", "pcm_kernel_loss",
+    "pcm_sinkhorn_schedule", "pcm_sinkhorn_workspace_bytes", "pcm_sinkhorn_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -220,6 +221,13 @@ def _open(path):
         L.pcm_kernel_loss_workspace_bytes.argtypes = [ci, ci, ci]
         L.pcm_kernel_loss.restype = ci
         L.pcm_kernel_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_sinkhorn_loss"):  # absent from A/B builds of older sources
+        L.pcm_sinkhorn_schedule.restype = ci
+        L.pcm_sinkhorn_schedule.argtypes = [cf, cf, cf, vp, ci]
+        L.pcm_sinkhorn_workspace_bytes.restype = cs
+        L.pcm_sinkhorn_workspace_bytes.argtypes = [ci, ci, ci]
+        L.pcm_sinkhorn_loss.restype = ci
+        L.pcm_sinkhorn_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1202,6 +1210,69 @@ def kernel_loss(xyz1, lay1, xyz2, lay2, kernel, blur, loss_out, gradxyz1=None, g
         _check(load_library().pcm_kernel_loss(_ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), int(kernel),
                                               float(blur), _ptr(loss_out), _ptr(gradxyz1), _ptr(gradxyz2),
                                               _ptr(workspace), workspace.numel(), _stream(dev)), "pcm_kernel_loss")
+
+
+SINKHORN_MAX_POINTS = 16384  # include/pcm.h PCM_SINKHORN_MAX_POINTS
+SINKHORN_MAX_STEPS = 128  # include/pcm.h PCM_SINKHORN_MAX_STEPS
+
+
+def sinkhorn_schedule(blur: float, scaling: float, diameter: float) -> list:
+    """pcm_sinkhorn_schedule: the epsilon list of pcm_sinkhorn_loss for
+    (blur, scaling, diameter) as Python floats -- diameter^2 twice, then down
+    by scaling^2 an entry while above blur^2, then blur^2.  Host only."""
+    eps = (ctypes.c_double * SINKHORN_MAX_STEPS)()
+    count = int(load_library().pcm_sinkhorn_schedule(float(blur), float(scaling), float(diameter), eps,
+                                                     SINKHORN_MAX_STEPS))
+    _check(min(count, 0), "pcm_sinkhorn_schedule")
+    return [float(eps[k]) for k in range(count)]
+
+
+def sinkhorn_workspace(dev: torch.device, b: int, n: int, m: int) -> torch.Tensor:
+    """Scratch for sinkhorn_loss (two halves of two float32 potentials per
+    point): ONE buffer per (device, current stream), grown when a larger
+    problem needs more; its content on entry is irrelevant and it holds nothing
+    between calls."""
+    need = max(int(load_library().pcm_sinkhorn_workspace_bytes(b, n, m)), 8)
+    key = ("sinkhorn", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def sinkhorn_loss(xyz1, lay1, xyz2, lay2, blur, scaling, diameter, loss_out, gradxyz1=None, gradxyz2=None,
+                  potentials=None, workspace=None) -> None:
+    """pcm_sinkhorn_loss on the float32 clouds xyz1 [B, N, 3] and xyz2
+    [B, M, 3] (each rows, or a view of channel planes: layout 1): loss_out [B]
+    = the debiased Sinkhorn divergence (p = 2, uniform weights) of every
+    element at `blur`, reached by epsilon-scaling with ratio `scaling` from
+    `diameter` (a host number: an upper bound of the clouds' extent);
+    gradxyz1 / gradxyz2 (each optional; its cloud's shape and layout) = the
+    gradient of loss_out[bi] in that cloud; potentials (optional, contiguous
+    [B, N + M, 2]) = the last step's (F_cross, F_own) of every point."""
+    tensors = (xyz1, xyz2, loss_out) + tuple(t for t in (gradxyz1, gradxyz2, potentials) if t is not None)
+    dev = _require_device(*tensors)
+    _knn_cloud(xyz1, lay1, "sinkhorn_loss")
+    _knn_cloud(xyz2, lay2, "sinkhorn_loss")
+    b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    if xyz2.shape[0] != b:
+        raise ValueError("sinkhorn_loss takes clouds of one batch size")
+    if loss_out.dtype != torch.float32 or tuple(loss_out.shape) != (b,) or not loss_out.is_contiguous():
+        raise ValueError(f"loss_out must be contiguous float32 of shape {(b,)}")
+    for g, x, lay in ((gradxyz1, xyz1, lay1), (gradxyz2, xyz2, lay2)):
+        if g is not None and (g.dtype != torch.float32 or g.shape != x.shape or cloud_layout(g) != int(lay)):
+            raise ValueError("a gradient must have its cloud's dtype, shape and layout")
+    if potentials is not None and (potentials.dtype != torch.float32 or tuple(potentials.shape) != (b, n + m, 2)
+                                   or not potentials.is_contiguous()):
+        raise ValueError(f"potentials must be contiguous float32 of shape {(b, n + m, 2)}")
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = sinkhorn_workspace(dev, b, n, m)
+        _check(load_library().pcm_sinkhorn_loss(_ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), float(blur),
+                                                float(scaling), float(diameter), _ptr(loss_out), _ptr(gradxyz1),
+                                                _ptr(gradxyz2), _ptr(potentials), _ptr(workspace),
+                                                workspace.numel(), _stream(dev)), "pcm_sinkhorn_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

@@ -731,6 +731,115 @@ int pcm_kernel_loss(const float *xyz1, const float *xyz2, int b, int n, int m, i
                     void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Sinkhorn divergence (debiased, balanced, p = 2, uniform weights)        */
+/* ---------------------------------------------------------------------- */
+
+/* Largest cloud (points per batch element) pcm_sinkhorn_loss takes and the
+ * longest epsilon schedule it runs (else PCM_ERR_UNSUPPORTED). */
+#define PCM_SINKHORN_MAX_POINTS 16384
+#define PCM_SINKHORN_MAX_STEPS 128
+
+/*
+ * Debiased Sinkhorn divergence of two unweighted clouds (extension): what
+ * geomloss's SamplesLoss(loss='sinkhorn', p=2, debias=True) computes for
+ * uniform weights.  geomloss is not installed where this library was written
+ * and could not be fetched: the algorithm below is the published one
+ * (sinkhorn_loop: symmetric averaged updates, epsilon-scaling, a last
+ * extrapolation step) and is NOT verified against that package.  This text is
+ * the contract.
+ *
+ * Contract.  Per batch element, cloud x = xyz1[bi] has n points of weight
+ *   a = 1/n and cloud y = xyz2[bi] has m points of weight b = 1/m; la = log a,
+ *   lb = log b.  Cost of a pair (p, q): C = d2 / 2 with (dx,dy,dz) = p - q in
+ *   float32 and d2 = fmaf(dz,dz,fmaf(dy,dy,dx*dx)) (the library's pinned
+ *   order).  softmin_eps(C, h)_i = -eps log sum_j exp(h_j - C_ij / eps).
+ *   Schedule (pcm_sinkhorn_schedule; host only, in double, no device call):
+ *   with D = diameter, s = scaling:  eps_0 = D^2;  eps_k = exp(2 ln D +
+ *   (k - 1) 2 ln s) for k = 1, 2, .. while 2 ln D + (k - 1) 2 ln s > 2 ln blur
+ *   (so eps_1 = eps_0, the published list's duplicate);  a last entry blur^2.
+ *   blur 0.05, scaling 0.5, D = sqrt(3) give T = 8 entries: 3, 3, 0.75, 0.1875,
+ *   0.046875, 0.01171875, 0.0029296875, 0.0025.  The function returns T and
+ *   fills eps_out[0..T) when eps_out is not NULL and capacity >= T.  A negative
+ *   return is a pcm_status: blur, scaling or diameter not finite, blur <= 0,
+ *   diameter <= 0, scaling outside (0, 1) -> PCM_ERR_INVALID_ARG; T above
+ *   PCM_SINKHORN_MAX_STEPS -> PCM_ERR_UNSUPPORTED.
+ *   Iteration.  At eps_0:  f_ba = softmin(C_xy, lb), g_ab = softmin(C_yx, la),
+ *   f_aa = softmin(C_xx, la), g_bb = softmin(C_yy, lb).  Then for every eps of
+ *   the schedule in order, all four from the OLD values,
+ *     ft_ba = softmin_eps(C_xy, lb + g_ab / eps),  gt_ab = softmin_eps(C_yx, la + f_ba / eps),
+ *     ft_aa = softmin_eps(C_xx, la + f_aa / eps),  gt_bb = softmin_eps(C_yy, lb + g_bb / eps),
+ *   and each potential becomes the mean 0.5 (old + new).  Last, at eps = blur^2,
+ *   one extrapolation without averaging, again from the old values:
+ *     F_ba = softmin(C_xy, lb + g_ab / eps),  G_ab = softmin(C_yx, la + f_ba / eps),
+ *     F_aa = softmin(C_xx, la + f_aa / eps),  G_bb = softmin(C_yy, lb + g_bb / eps).
+ *   loss_out[bi] = sum_i a (F_ba,i - F_aa,i) + sum_j b (G_ab,j - G_bb,j): in
+ *   double, row r of the concatenation x || y contributes w_r (F_cross - F_own)
+ *   in pcm_kernel_loss's fixed order (thread t of 256 adds rows t, t + 256, ..
+ *   ascending, every wave its 64 threads by the six DPP steps, the four waves'
+ *   sums ascending); rounded once to float32.
+ *   Gradients: of loss_out[bi] with unit upstream gradient, from the
+ *   extrapolation step with the averaged potentials (and the column points)
+ *   held fixed -- the envelope rule:
+ *     gradxyz1[i] = a (sum_k Q_ik x_k - sum_j P_ij y_j),
+ *   P_i. the softmax over j of (lb + g_ab / eps - C_xy / eps), Q_i. the softmax
+ *   over k of (la + f_aa / eps - C_xx / eps); gradxyz2 with the roles swapped.
+ *   The kernel forms the same quantity as a (sum_j P_ij (x_i - y_j) -
+ *   sum_k Q_ik (x_i - x_k)) from the differences it already holds.  Each
+ *   gradient is nullable on its own, has its cloud's shape AND layout and is
+ *   fully overwritten; a NULL gradient pointer changes no other output by a bit.
+ *   potentials_out (NULL, or [b, n + m, 2] float32): for row r of x || y the
+ *   pair (F_cross, F_own) -- diagnostics and parity tests, as `price` is in
+ *   pcm_emd_forward.
+ *   Numerics.  float32 throughout the scans, in base 2 on the hardware
+ *   v_exp_f32 / v_log_f32: a column carries h2 = fmaf(potential,
+ *   fl(log2(e) / eps), fl(-log2 count)), a pair's exponent is t = fmaf(d2,
+ *   fl(-log2(e) / (2 eps)), h2), and a softmin is (M + log2 sum 2^(t - M)) *
+ *   fl(-eps ln 2) with M the running maximum of t, so no sum overflows or is
+ *   empty for finite input.  The three per-step constants are formed in double
+ *   from the schedule's double eps and rounded once.
+ *   Order.  A softmin over a cloud of c points: eight partial (max, sum) pairs,
+ *   partial w over the points q with (q mod 1024) div 128 == w, q ascending in
+ *   groups of four (then single points up to the end of the share): the group's
+ *   maximum joins the running one, the running sum is rescaled by
+ *   2^(old max - new max) (skipped where it is 1 for a whole wave: the same
+ *   bits), then the group's terms are added in order; the
+ *   partials merge as (((p0 + p1) + p2) + ..) + p7, each merge rescaling both
+ *   sides to the larger maximum.  The own cloud is scanned first.  No float
+ *   atomics; the order of every sum depends on (n, m) alone: results are
+ *   bit-identical from run to run, across layouts, and element bi of a batch
+ *   equals the same clouds evaluated alone (b = 1) bit for bit.
+ *   Non-finite input: a NaN coordinate makes loss_out of ITS element NaN and
+ *   leaves the other elements' outputs untouched; that element's gradients are
+ *   unspecified.  The call always returns.
+ * layout1 / layout2: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, each
+ *   cloud read in place and its gradient written in the same layout.
+ * T + 3 launches on `stream` (the initialisation, one per schedule entry, the
+ *   extrapolation, the loss finish), capturable; no host synchronisation, no
+ *   allocation, no waiting between workgroups.  `diameter` is a host argument
+ *   so that nothing is read back.  The workspace
+ *   (pcm_sinkhorn_workspace_bytes(b, n, m) bytes, 8-byte aligned) holds two
+ *   halves of (cross, own) potentials a point that the steps ping-pong
+ *   between; it needs no initialisation and keeps no state.
+ * Validation, before any device call: negative sizes, a layout outside {0, 1},
+ *   a schedule error (PCM_ERR_INVALID_ARG, or PCM_ERR_UNSUPPORTED for too many
+ *   steps); then b == 0 is a no-op (PCM_OK, also with null pointers); n == 0,
+ *   m == 0, a null cloud or loss_out -> PCM_ERR_INVALID_ARG; n or m above
+ *   PCM_SINKHORN_MAX_POINTS (or b beyond the grid) -> PCM_ERR_UNSUPPORTED:
+ *   nothing is launched; a workspace that is NULL or too short ->
+ *   PCM_ERR_WORKSPACE; a misaligned one -> PCM_ERR_INVALID_ARG.
+ * pcm_sinkhorn_workspace_bytes: 0 when b, n or m is not positive.
+ */
+int pcm_sinkhorn_schedule(float blur, float scaling, float diameter, double *eps_out /* NULL or [capacity] */,
+                          int capacity);
+size_t pcm_sinkhorn_workspace_bytes(int b, int n, int m);
+int pcm_sinkhorn_loss(const float *xyz1, const float *xyz2, int b, int n, int m, int layout1, int layout2,
+                      float blur, float scaling, float diameter, float *loss_out /* [b] */,
+                      float *gradxyz1 /* NULL or xyz1's shape and layout */,
+                      float *gradxyz2 /* NULL or xyz2's shape and layout */,
+                      float *potentials_out /* NULL or [b, n + m, 2] */, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
 /* ---------------------------------------------------------------------- */
 
