@@ -4,7 +4,8 @@ Same class and method names/signatures (loss/loss.py:12-37): ``Loss`` with
 ``get_emd_loss(pred, gt, radius=1.0)`` and ``get_chamfer_loss(pred, gt)``, so
 train.py:162-171 calls it unchanged, plus ``get_repulsion_loss(pcd, h)`` and
 ``get_uniform_loss(pcd, percentage, radius)``, which the reference dropped, and
-``get_sinkhorn_loss(pred, gt, blur, scaling, diameter)`` (an extension).  Fixes the reference's module-scope
+``get_sinkhorn_loss(pred, gt, blur, scaling, diameter)`` and
+``get_sliced_loss(pred, gt, n_projections)`` (extensions).  Fixes the reference's module-scope
 ``torch`` NameError (loss/loss.py:25 vs :40) and
 resolves the metric modules relative to this file instead of the working
 directory (loss/loss.py:1-7).
@@ -32,6 +33,7 @@ if _HERE not in sys.path:
 from repulsion_loss import repulsion_lossFunction  # noqa: E402
 from uniform_loss import uniform_lossFunction  # noqa: E402
 import sinkhorn_loss as sinkhorn  # noqa: E402
+import sliced_loss as sliced  # noqa: E402
 
 UNIFORM_MAX_NSAMPLE = 64  # pcm_hip.BALL_MAX_NSAMPLE: the longest group of one scale
 
@@ -134,6 +136,15 @@ class Loss(nn.Module):
         pass an upper bound of it to keep the call capturable."""
         return torch.mean(sinkhorn.SamplesLoss("sinkhorn", p=2, blur=blur, scaling=scaling,
                                                diameter=diameter)(pred, gt))
+
+    def get_sliced_loss(self, pred, gt, n_projections=128):
+        """pred is B x N x 3 and gt is B x M x 3 (any N and M): the batch mean
+        of the sliced 2-Wasserstein distance over ``n_projections`` random unit
+        directions drawn anew on every call, one pcm_sliced_wasserstein_loss
+        call (loss/sliced_loss.py), differentiable in both clouds.  The
+        gradient is written in the input's layout, so the generator's
+        ``fake.transpose(2, 1)`` is read in place."""
+        return torch.mean(sliced.SlicedWassersteinLoss(n_projections=n_projections)(pred, gt))
 
 
 if __name__ == "__main__":

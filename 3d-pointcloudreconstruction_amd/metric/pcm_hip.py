@@ -44,6 +44,7 @@ EXPORTED = (
     "pcm_ball_query", "pcm_uniform_workspace_bytes", "pcm_uniform_loss",
     "pcm_kernel_loss_workspace_bytes", "pcm_kernel_loss",
     "pcm_sinkhorn_schedule", "pcm_sinkhorn_workspace_bytes", "pcm_sinkhorn_loss",
+    "pcm_sliced_workspace_bytes", "pcm_sliced_wasserstein_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -228,6 +229,12 @@ def _open(path):
         L.pcm_sinkhorn_workspace_bytes.argtypes = [ci, ci, ci]
         L.pcm_sinkhorn_loss.restype = ci
         L.pcm_sinkhorn_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_sliced_wasserstein_loss"):  # absent from A/B builds of older sources
+        L.pcm_sliced_workspace_bytes.restype = cs
+        L.pcm_sliced_workspace_bytes.argtypes = [ci, ci, ci, ci]
+        L.pcm_sliced_wasserstein_loss.restype = ci
+        L.pcm_sliced_wasserstein_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, cs,
+                                                  vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1273,6 +1280,69 @@ def sinkhorn_loss(xyz1, lay1, xyz2, lay2, blur, scaling, diameter, loss_out, gra
                                                 float(scaling), float(diameter), _ptr(loss_out), _ptr(gradxyz1),
                                                 _ptr(gradxyz2), _ptr(potentials), _ptr(workspace),
                                                 workspace.numel(), _stream(dev)), "pcm_sinkhorn_loss")
+
+
+SLICED_MAX_POINTS = 16384  # include/pcm.h PCM_SLICED_MAX_POINTS
+SLICED_MAX_DIRS = 1024  # include/pcm.h PCM_SLICED_MAX_DIRS
+SLICED_FUSED_MAX_POINTS = 2048  # include/pcm.h PCM_SLICED_FUSED_MAX_POINTS
+
+
+def sliced_workspace_bytes(b: int, n: int, m: int, l: int) -> int:
+    return int(load_library().pcm_sliced_workspace_bytes(int(b), int(n), int(m), int(l)))
+
+
+def sliced_workspace(dev: torch.device, b: int, n: int, m: int, l: int) -> torch.Tensor:
+    """Scratch for sliced_wasserstein_loss (the slices, the points'
+    coefficients and, for large clouds, the sorted lists): ONE buffer per
+    (device, current stream), grown when a larger problem needs more; its
+    content on entry is irrelevant and it holds nothing between calls."""
+    need = max(sliced_workspace_bytes(b, n, m, l), 8)
+    key = ("sliced", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def sliced_wasserstein_loss(xyz1, lay1, xyz2, lay2, dirs, loss_out, slices=None, gradxyz1=None, gradxyz2=None,
+                            order1=None, order2=None, workspace=None) -> None:
+    """pcm_sliced_wasserstein_loss on the float32 clouds xyz1 [B, N, 3] and
+    xyz2 [B, M, 3] (each rows, or a view of channel planes: layout 1) and the
+    contiguous float32 directions dirs [L, 3] (taken as given): loss_out [B] =
+    the mean over the directions of the exact 1-D transport cost of the
+    projections; slices (optional, contiguous [B, L]) = every direction's
+    cost; gradxyz1 / gradxyz2 (each optional; its cloud's shape and layout) =
+    the gradient of loss_out[bi] in that cloud; order1 / order2 (optional,
+    contiguous int32 [B, L, N] / [B, L, M]) = the point of every rank."""
+    optional = (slices, gradxyz1, gradxyz2, order1, order2)
+    dev = _require_device(xyz1, xyz2, dirs, loss_out, *(t for t in optional if t is not None))
+    _knn_cloud(xyz1, lay1, "sliced_wasserstein_loss")
+    _knn_cloud(xyz2, lay2, "sliced_wasserstein_loss")
+    b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    if xyz2.shape[0] != b:
+        raise ValueError("sliced_wasserstein_loss takes clouds of one batch size")
+    if dirs.dtype != torch.float32 or dirs.dim() != 2 or dirs.shape[1] != 3 or not dirs.is_contiguous():
+        raise ValueError("dirs must be contiguous float32 of shape [L, 3]")
+    l = dirs.shape[0]
+    if loss_out.dtype != torch.float32 or tuple(loss_out.shape) != (b,) or not loss_out.is_contiguous():
+        raise ValueError(f"loss_out must be contiguous float32 of shape {(b,)}")
+    if slices is not None and (slices.dtype != torch.float32 or tuple(slices.shape) != (b, l)
+                               or not slices.is_contiguous()):
+        raise ValueError(f"slices must be contiguous float32 of shape {(b, l)}")
+    for g, x, lay in ((gradxyz1, xyz1, lay1), (gradxyz2, xyz2, lay2)):
+        if g is not None and (g.dtype != torch.float32 or g.shape != x.shape or cloud_layout(g) != int(lay)):
+            raise ValueError("a gradient must have its cloud's dtype, shape and layout")
+    for o, cnt in ((order1, n), (order2, m)):
+        if o is not None and (o.dtype != torch.int32 or tuple(o.shape) != (b, l, cnt) or not o.is_contiguous()):
+            raise ValueError(f"an order output must be contiguous int32 of shape {(b, l, cnt)}")
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = sliced_workspace(dev, b, n, m, l)
+        _check(load_library().pcm_sliced_wasserstein_loss(
+            _ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), _ptr(dirs), l, _ptr(loss_out), _ptr(slices),
+            _ptr(gradxyz1), _ptr(gradxyz2), _ptr(order1), _ptr(order2), _ptr(workspace), workspace.numel(),
+            _stream(dev)), "pcm_sliced_wasserstein_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

@@ -840,6 +840,105 @@ int pcm_sinkhorn_loss(const float *xyz1, const float *xyz2, int b, int n, int m,
                       void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Sliced Wasserstein distance (p = 2, uniform masses)                     */
+/* ---------------------------------------------------------------------- */
+
+/* Largest cloud (points per batch element) and most directions
+ * pcm_sliced_wasserstein_loss takes (else PCM_ERR_UNSUPPORTED). */
+#define PCM_SLICED_MAX_POINTS 16384
+#define PCM_SLICED_MAX_DIRS   1024
+/* Switch-over: with both clouds at or below it one workgroup projects, sorts
+ * and matches an (element, direction) out of LDS in one launch; above it each
+ * cloud is sorted by a workgroup of its own and the sorted (key, index)
+ * composites pass through the workspace.  Results do not depend on the path. */
+#define PCM_SLICED_FUSED_MAX_POINTS 2048
+
+/*
+ * Sliced 2-Wasserstein distance of two unweighted clouds (extension; Nguyen et
+ * al., "Point-set distances for learning representations of 3D point clouds"):
+ * the mean over l directions of the exact 1-D transport cost between the
+ * clouds' projections.  This text is the contract.
+ *
+ * Per batch element, cloud x = xyz1[bi] has n points of mass 1/n and cloud
+ *   y = xyz2[bi] has m points of mass 1/m.  The l directions theta = dirs[li]
+ *   (device memory, [l, 3] float32, contiguous) are taken as given -- the
+ *   library does not normalise them -- and are shared by the batch.
+ * Projection, pinned: p = fmaf(tz, z, fmaf(ty, y, tx * x)) in float32, explicit
+ *   fused steps and no other contraction.
+ * Order, pinned and total: the key of p is u = bits(p), then u ^ 0xFFFFFFFF if
+ *   the sign bit is set, else u | 0x80000000, compared as unsigned: -0.0 sorts
+ *   before +0.0 and NaNs sort by their bits at the two ends.  Equal keys are
+ *   ordered by ascending point index.  order1_out[bi, li, r] (NULL or
+ *   [b, l, n] int32) is the index of the point of rank r; order2_out the same
+ *   for y.  They EQUAL np.lexsort((index, key)).
+ * Matching, exact 1-D transport of uniform masses: rank r of x covers the
+ *   quantile interval [r/n, (r+1)/n) and overlaps ranks s of y from
+ *   (r m) div n to ceil((r+1) m / n) - 1 with the integer weight
+ *   w_rs = min((r+1) m, (s+1) n) - max(r m, s n).  With a, b the sorted
+ *   projections,
+ *     slice = (1 / (n m)) sum_r sum_s w_rs (a_r - b_s)^2
+ *   (for n = m: (1/n) sum_r (a_r - b_r)^2);  slices_out[bi, li] (NULL or
+ *   [b, l]) = slice rounded once;  loss_out[bi] = (1/l) sum_li slice,
+ *   accumulated in double and rounded once.
+ * Gradients of loss_out[bi] with unit upstream gradient:
+ *     gradxyz1[i] = (1/l) sum_li theta_li (2 / (n m)) sum_s w_rs (a_r - b_s),
+ *   r the rank of i in slice li;  gradxyz2[j] the same with the roles swapped
+ *   and the sign flipped ((2 / (n m)) sum_r w_rs (b_s - a_r)).  In exact
+ *   arithmetic sum_i gradxyz1 + sum_j gradxyz2 = 0.  Each gradient is nullable
+ *   on its own, has its cloud's shape AND layout and is fully overwritten; a
+ *   NULL pointer for any optional output changes no other output by a bit.
+ * Numerics and order of the sums.  a_r - b_s, the products with w_rs and all
+ *   sums are in double.  A slice: a thread adds its ranks r ascending and for
+ *   each the ranks s ascending (up to the fused size the thread of cloud x's
+ *   E = 4 or 16 consecutive ranks, above it ranks t, t + 256, .. of 256
+ *   threads); every wave adds its 64 threads by the six DPP steps, the waves'
+ *   sums are added ascending; the total is divided by (double) n m.  A point's
+ *   coefficient c = fl32((2 / (n m)) sum_s w_rs (a_r - b_s)) is rounded to
+ *   float32 once; its gradient is four partial sums of (double) theta_li *
+ *   (double) c, partial w over li in [w q, min(l, (w + 1) q)), q = ceil(l / 4),
+ *   ascending, added in order, divided by l, rounded once.  loss_out: thread t
+ *   of 256 adds the slices t, t + 256, .., then waves and workgroup as above,
+ *   divided by l.
+ *   No float atomics, no waiting between workgroups; the order of every sum
+ *   depends on (n, m, l) alone: results are bit-identical from run to run,
+ *   across layouts, and element bi of a batch equals the same clouds evaluated
+ *   alone (b = 1) bit for bit.
+ * Non-finite input: the order stays total, so the call always returns and
+ *   never indexes out of range.  An element with a NaN coordinate gets a NaN
+ *   loss_out; its order*_out still equal the lexsort of the keys of the
+ *   projections the device's fused multiply-adds give (a NaN operand comes
+ *   through with its sign and payload, quieted); its gradients are
+ *   unspecified.  The other elements' outputs are untouched, bit for bit.
+ * layout1 / layout2: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, each
+ *   cloud read in place and its gradient written in the same layout.
+ * Launches on `stream`: two (sort-and-match, finish) when both clouds are at
+ *   most PCM_SLICED_FUSED_MAX_POINTS, else three (sort, match, finish) -- a
+ *   fixed function of the shape; capturable; no host synchronisation, no
+ *   allocation.  The workspace (pcm_sliced_workspace_bytes(b, n, m, l) bytes,
+ *   8-byte aligned: b l doubles for the slices, b l (n + m) floats for the
+ *   points' coefficients by original index and, above the fused size,
+ *   b l (n + m) 8-byte sorted composites) needs no initialisation and keeps no
+ *   state.
+ * Validation, before any device call: negative sizes, a layout outside {0, 1},
+ *   l <= 0 -> PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK, also with
+ *   null pointers); n == 0, m == 0, a null cloud, dirs or loss_out ->
+ *   PCM_ERR_INVALID_ARG; n or m above PCM_SLICED_MAX_POINTS, l above
+ *   PCM_SLICED_MAX_DIRS (or b l beyond the grid) -> PCM_ERR_UNSUPPORTED; a
+ *   workspace that is NULL or too short -> PCM_ERR_WORKSPACE; a misaligned one
+ *   -> PCM_ERR_INVALID_ARG.
+ * pcm_sliced_workspace_bytes: 0 when b, n, m or l is not positive.
+ */
+size_t pcm_sliced_workspace_bytes(int b, int n, int m, int l);
+int pcm_sliced_wasserstein_loss(const float *xyz1, const float *xyz2, int b, int n, int m, int layout1, int layout2,
+                                const float *dirs /* device, [l, 3] */, int l, float *loss_out /* [b] */,
+                                float *slices_out /* NULL or [b, l] */,
+                                float *gradxyz1 /* NULL or xyz1's shape and layout */,
+                                float *gradxyz2 /* NULL or xyz2's shape and layout */,
+                                int32_t *order1_out /* NULL or [b, l, n] */,
+                                int32_t *order2_out /* NULL or [b, l, m] */, void *workspace, size_t workspace_bytes,
+                                void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
 /* ---------------------------------------------------------------------- */
 
