@@ -5,7 +5,8 @@ Same class and method names/signatures (loss/loss.py:12-37): ``Loss`` with
 train.py:162-171 calls it unchanged, plus ``get_repulsion_loss(pcd, h)`` and
 ``get_uniform_loss(pcd, percentage, radius)``, which the reference dropped, and
 ``get_sinkhorn_loss(pred, gt, blur, scaling, diameter)`` and
-``get_sliced_loss(pred, gt, n_projections)`` (extensions).  Fixes the reference's module-scope
+``get_sliced_loss(pred, gt, n_projections)`` and
+``get_dcd_loss(pred, gt, alpha, n_lambda)`` (extensions).  Fixes the reference's module-scope
 ``torch`` NameError (loss/loss.py:25 vs :40) and
 resolves the metric modules relative to this file instead of the working
 directory (loss/loss.py:1-7).
@@ -34,6 +35,7 @@ from repulsion_loss import repulsion_lossFunction  # noqa: E402
 from uniform_loss import uniform_lossFunction  # noqa: E402
 import sinkhorn_loss as sinkhorn  # noqa: E402
 import sliced_loss as sliced  # noqa: E402
+import dcd_loss as dcd  # noqa: E402
 
 UNIFORM_MAX_NSAMPLE = 64  # pcm_hip.BALL_MAX_NSAMPLE: the longest group of one scale
 
@@ -145,6 +147,16 @@ class Loss(nn.Module):
         gradient is written in the input's layout, so the generator's
         ``fake.transpose(2, 1)`` is read in place."""
         return torch.mean(sliced.SlicedWassersteinLoss(n_projections=n_projections)(pred, gt))
+
+    def get_dcd_loss(self, pred, gt, alpha=1000, n_lambda=1):
+        """pred is B x N x 3 and gt is B x M x 3 (any N and M): the batch mean
+        of the density-aware Chamfer distance, one pcm_dcd_loss call
+        (loss/dcd_loss.py), differentiable in both clouds.  The gradient is
+        written in the input's layout, so the generator's
+        ``fake.transpose(2, 1)`` is read in place.  ``alpha = 1000`` is the
+        published default for clouds of about 2048 points or more in a unit
+        box; coarser clouds need a smaller one (loss/dcd_loss.py)."""
+        return dcd.DCDLoss(alpha=alpha, n_lambda=n_lambda)(pred, gt)
 
 
 if __name__ == "__main__":

@@ -45,6 +45,7 @@ EXPORTED = (
     "pcm_kernel_loss_workspace_bytes", "pcm_kernel_loss",
     "pcm_sinkhorn_schedule", "pcm_sinkhorn_workspace_bytes", "pcm_sinkhorn_loss",
     "pcm_sliced_workspace_bytes", "pcm_sliced_wasserstein_loss",
+    "pcm_dcd_workspace_bytes", "pcm_dcd_loss",
     "pcm_icp_workspace_bytes", "pcm_icp", "pcm_icp_workspace_status", "pcm_nearest_neighbor",
     "pcm_best_fit_transform",
     "pcm_npy_cloud_points", "pcm_npy_load_clouds",
@@ -235,6 +236,11 @@ def _open(path):
         L.pcm_sliced_wasserstein_loss.restype = ci
         L.pcm_sliced_wasserstein_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, cs,
                                                   vp]
+    if hasattr(L, "pcm_dcd_loss"):  # absent from A/B builds of older sources
+        L.pcm_dcd_workspace_bytes.restype = cs
+        L.pcm_dcd_workspace_bytes.argtypes = [ci, ci, ci]
+        L.pcm_dcd_loss.restype = ci
+        L.pcm_dcd_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, cs, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1343,6 +1349,66 @@ def sliced_wasserstein_loss(xyz1, lay1, xyz2, lay2, dirs, loss_out, slices=None,
             _ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), _ptr(dirs), l, _ptr(loss_out), _ptr(slices),
             _ptr(gradxyz1), _ptr(gradxyz2), _ptr(order1), _ptr(order2), _ptr(workspace), workspace.numel(),
             _stream(dev)), "pcm_sliced_wasserstein_loss")
+
+
+DCD_MAX_POINTS = 16384  # include/pcm.h PCM_DCD_MAX_POINTS
+
+
+def dcd_workspace_bytes(b: int, n: int, m: int) -> int:
+    return int(load_library().pcm_dcd_workspace_bytes(int(b), int(n), int(m)))
+
+
+def dcd_workspace(dev: torch.device, b: int, n: int, m: int) -> torch.Tensor:
+    """Scratch for dcd_loss (the forward's distances and argmins, the grid
+    forward's own bytes for large clouds, the graddists and a gradient each):
+    ONE buffer per (device, current stream), grown when a larger problem needs
+    more; its content on entry is irrelevant and it holds nothing between
+    calls."""
+    need = max(dcd_workspace_bytes(b, n, m), 16)
+    key = ("dcd", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def dcd_loss(xyz1, lay1, xyz2, lay2, alpha, n_lambda, non_reg, loss_out, cd=None, gradxyz1=None, gradxyz2=None,
+             count1=None, count2=None, graddist1=None, graddist2=None, workspace=None) -> None:
+    """pcm_dcd_loss on the float32 clouds xyz1 [B, N, 3] and xyz2 [B, M, 3]
+    (each rows, or a view of channel planes: layout 1): loss_out [B] = the
+    density-aware Chamfer distance at ``alpha`` and ``n_lambda``; cd
+    (optional, contiguous [B, 2]) = cd_p and cd_t; gradxyz1 / gradxyz2 (each
+    optional; its cloud's shape and layout) = the gradient of loss_out[bi] in
+    that cloud; count1 / count2 (optional, contiguous int32 [B, N] / [B, M]) =
+    how many points of the other cloud have each point as their neighbour;
+    graddist1 / graddist2 (optional, contiguous [B, N] / [B, M]) = the
+    per-point weights the Chamfer backward is fed."""
+    optional = (cd, gradxyz1, gradxyz2, count1, count2, graddist1, graddist2)
+    dev = _require_device(xyz1, xyz2, loss_out, *(t for t in optional if t is not None))
+    _knn_cloud(xyz1, lay1, "dcd_loss")
+    _knn_cloud(xyz2, lay2, "dcd_loss")
+    b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
+    if xyz2.shape[0] != b:
+        raise ValueError("dcd_loss takes clouds of one batch size")
+    if loss_out.dtype != torch.float32 or tuple(loss_out.shape) != (b,) or not loss_out.is_contiguous():
+        raise ValueError(f"loss_out must be contiguous float32 of shape {(b,)}")
+    if cd is not None and (cd.dtype != torch.float32 or tuple(cd.shape) != (b, 2) or not cd.is_contiguous()):
+        raise ValueError(f"cd must be contiguous float32 of shape {(b, 2)}")
+    for g, x, lay in ((gradxyz1, xyz1, lay1), (gradxyz2, xyz2, lay2)):
+        if g is not None and (g.dtype != torch.float32 or g.shape != x.shape or cloud_layout(g) != int(lay)):
+            raise ValueError("a gradient must have its cloud's dtype, shape and layout")
+    for t, dtype, cnt in ((count1, torch.int32, n), (count2, torch.int32, m), (graddist1, torch.float32, n),
+                          (graddist2, torch.float32, m)):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (b, cnt) or not t.is_contiguous()):
+            raise ValueError(f"a per-point output must be contiguous {dtype} of shape {(b, cnt)}")
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = dcd_workspace(dev, b, n, m)
+        _check(load_library().pcm_dcd_loss(
+            _ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), float(alpha), float(n_lambda), int(bool(non_reg)),
+            _ptr(loss_out), _ptr(cd), _ptr(gradxyz1), _ptr(gradxyz2), _ptr(count1), _ptr(count2), _ptr(graddist1),
+            _ptr(graddist2), _ptr(workspace), workspace.numel(), _stream(dev)), "pcm_dcd_loss")
 
 
 def emd_workspace_bytes(b: int, n: int) -> int:

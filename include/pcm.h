@@ -939,6 +939,100 @@ int pcm_sliced_wasserstein_loss(const float *xyz1, const float *xyz2, int b, int
                                 void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Density-aware Chamfer distance                                          */
+/* ---------------------------------------------------------------------- */
+
+/* Largest cloud (points per batch element) pcm_dcd_loss takes (else
+ * PCM_ERR_UNSUPPORTED): both clouds' hit counts of one element live in one
+ * workgroup's LDS, 2 x 16384 x 4 bytes. */
+#define PCM_DCD_MAX_POINTS 16384
+
+/*
+ * Density-aware Chamfer distance (extension; Wu et al., "Density-aware Chamfer
+ * Distance as a Comprehensive Metric for Point Cloud Completion", NeurIPS
+ * 2021).  The formula is stated from the published source, not verified
+ * against it (the package is not installed where this was written); this text
+ * is the contract.
+ *
+ * Per batch element, for xyz1 [b, n, 3] and xyz2 [b, m, 3]:
+ *   d1, i1, d2, i2 are exactly what pcm_chamfer_forward returns for the clouds
+ *   (squared distances in the pinned order, lowest-index argmins).
+ *   Hit counts: count2[k] = #{j : i1[j] = k} (how many points of xyz1 have
+ *   xyz2[k] as their neighbour), count1[j] = #{k : i2[k] = j}.
+ *   count1_out (NULL or [b, n] int32) and count2_out (NULL or [b, m] int32)
+ *   EQUAL np.bincount of the argmins.
+ *   Direction 1 has the n points of xyz1 as queries into the m targets of
+ *   xyz2, direction 2 the reverse.  The ratio of a direction with Q queries
+ *   and T targets is r = (float)Q / (float)T, or with non_reg != 0
+ *   r = max(1.f, (float)Q / (float)T).
+ *   term(q) = 1 - exp(-alpha d(q)) r / (c(idx(q))^lambda + 1e-6), c the TARGET
+ *   cloud's counts (direction 1: count2[i1[j]]; a query's own target has
+ *   c >= 1);
+ *   loss_out[bi] = (mean_j term1(j) + mean_k term2(k)) / 2.
+ *   cd_out (NULL or [b, 2]): cd_out[bi, 0] = (mean_j sqrt(d1) + mean_k sqrt(d2)) / 2
+ *   ("cd_p"), cd_out[bi, 1] = mean_j d1 + mean_k d2 ("cd_t").
+ * float32 evaluation order of a term, pinned (every operation rounded once, no
+ * contraction):
+ *     a = alpha * d;  e = expf(-a)   (the device library's expf, not the
+ *                                     hardware's approximate exponential);
+ *     p = c (the count converted, exact) when lambda == 1, 1.f when
+ *         lambda == 0, else powf((float)c, lambda): lambda == 1 never calls powf;
+ *     w = (1.f / (p + 1e-6f)) * r;   r multiplies the reciprocal, not e;
+ *     g = e * w;  term = 1.f - g;
+ *     graddist = (alpha * g) / (float)(2 Q).
+ * Sums: a thread adds the terms of queries t, t + 1024, ... (a workgroup of
+ *   1024 threads) ascending in double, sqrtf(d) and d likewise; a wave adds
+ *   its 64 lanes by the six DPP steps, the waves' sums are added ascending (cd_t
+ *   is the plain sum of the two directions' means); each sum is divided
+ *   by its query count in double, the two directions are added, halved (loss,
+ *   cd_p) and rounded to float32 once.  One workgroup holds an element, so no
+ *   sum crosses workgroups.
+ * Gradients.  The counts carry no gradient (the published code detaches them):
+ *   graddist1[j] = alpha r1 exp(-alpha d1[j]) / (count2[i1[j]]^lambda + 1e-6) / (2 n),
+ *   graddist2[k] the same with r2, count1[i2[k]] and 2 m, both in the order
+ *   pinned above.  graddist1_out (NULL or [b, n]) and graddist2_out (NULL or
+ *   [b, m]) receive them; gradxyz1 / gradxyz2 (each NULL or its cloud's shape
+ *   AND layout) are what pcm_chamfer_backward_strided gives for these
+ *   graddists, bit for bit -- the gradient of loss_out[bi] with unit upstream
+ *   gradient.  A NULL pointer for any optional output changes no other output
+ *   by a bit; every output element is fully overwritten.
+ * Non-finite input.  A query whose distance is +inf has e = 0: term 1,
+ *   graddist 0.  A NaN distance gives that element a NaN loss; argmins stay in
+ *   range (pcm_chamfer_forward's tile rule), the counts are still their
+ *   bincount, and the other elements' outputs are untouched, bit for bit.
+ * Launches on `stream`: the forward exactly as pcm_chamfer_forward_ws picks it
+ *   for row clouds (the grid forward when both clouds hold >= 4096 points and
+ *   b n m >= 2^28, else the dense kernels) or pcm_chamfer_forward_layout when
+ *   a cloud is in channel planes; ONE launch for counts, terms, graddists and
+ *   sums (one workgroup an element; integer LDS atomics only, whose sums do not
+ *   depend on their order); pcm_chamfer_backward_strided only when a gradient
+ *   is asked for.  Deterministic: no float atomics, no waiting between
+ *   workgroups; element bi of a batch equals the same clouds evaluated alone.
+ *   Capturable: no host synchronisation, no allocation, no state.
+ *   The workspace (pcm_dcd_workspace_bytes(b, n, m) bytes, 16-byte aligned:
+ *   the grid forward's bytes when that path is taken, d and i of both
+ *   directions, the graddists and a gradient each for the pointers that may be
+ *   NULL) needs no initialisation.
+ * layout1 / layout2: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, each
+ *   cloud read in place and its gradient written in the same layout.
+ * Validation, before any device call: negative sizes, a layout outside {0, 1},
+ *   alpha not finite or <= 0, n_lambda not finite or < 0 ->
+ *   PCM_ERR_INVALID_ARG; then b == 0 is a no-op (PCM_OK, also with null
+ *   pointers); n == 0, m == 0, a null cloud or loss_out -> PCM_ERR_INVALID_ARG;
+ *   n or m above PCM_DCD_MAX_POINTS -> PCM_ERR_UNSUPPORTED; a workspace that is
+ *   NULL or too short -> PCM_ERR_WORKSPACE; a misaligned one ->
+ *   PCM_ERR_INVALID_ARG.
+ * pcm_dcd_workspace_bytes: 0 when b, n or m is not positive.
+ */
+size_t pcm_dcd_workspace_bytes(int b, int n, int m);
+int pcm_dcd_loss(const float *xyz1, const float *xyz2, int b, int n, int m, int layout1, int layout2, float alpha,
+                 float n_lambda, int non_reg, float *loss_out /* [b] */, float *cd_out /* NULL or [b, 2] */,
+                 float *gradxyz1 /* NULL or xyz1's shape and layout */,
+                 float *gradxyz2 /* NULL or xyz2's shape and layout */, int32_t *count1_out /* NULL or [b, n] */,
+                 int32_t *count2_out /* NULL or [b, m] */, float *graddist1_out /* NULL or [b, n] */,
+                 float *graddist2_out /* NULL or [b, m] */, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* EMD (auction approximation)                                           */
 /* ---------------------------------------------------------------------- */
 
