@@ -425,6 +425,11 @@ int pcm_proj_bce(const float *pred, const float *gt, long long count, float w, f
  *   every point of a cloud of distinct finite points is taken, index 0
  *   repeats); a point with a NaN coordinate keeps run = 1e10f and, once it is
  *   the lowest such point, repeats for the rest of the call.
+ *   Squared distances of 1e10 and above (coordinates around 1e5) never lower
+ *   the 1e10f start value: the points they leave saturated all attain the
+ *   maximum, so the seeds follow index order among the saturated points, as
+ *   the reference's do (tests/test_geometry_gpu.py pins this on a cloud
+ *   scaled by 2e5).
  *   The reference forms d as a torch sum of three squares; where its winner
  *   beats the runner-up by more than a few float32 ulps, or ties it exactly,
  *   the indices are the same.

@@ -29,6 +29,16 @@ They follow the pinned chain of the header, u = 2^-24 a rounding:
   so  |err g| <= RHO g,  RHO = (a + K) u (1 + 2^-10),  K = 11, or 43 with powf;
   the factor (1 + 2^-10) covers the second-order terms ((a + K) u < 2^-10 for
   a < 16000, beyond which exp(-a) is 0 in float32 and in float64 alike).
+  Beyond a = 16000 (one outlier far from a cloud whose alpha comes from the
+  median: tests/geometry_cases.py's far_point has a = 1e6) RHO itself is no
+  longer small, but it multiplies nothing: the float32 a = fl(alpha d) is at
+  least 16000 (1 - u) > 745, so expf(-a) and the double exp alike return 0
+  exactly, g = 0, term = fl(1 - 0) = 1 and graddist = 0 in both precisions,
+  and the bounds below reduce to their g-free parts (2^-126 and u |term|, and
+  alpha 2^-126 / (2 Q) + 2^-149), which such a term meets with error 0.  All
+  that is needed of a is that it be finite, i.e. alpha d below 3.4e38.
+  tests/test_geometry_cpu.py asserts e = g = graddist = 0 and term = 1 there
+  for the float32 and the float64 evaluation.
   A g below the normal range may lose its last bits or be flushed: + 2^-126.
     term = fl(1 - g)         |err term| <= RHO g + 2^-126 + u |1 - g|.
     loss                     the mean of the terms' errors of each direction,

@@ -102,6 +102,23 @@ def restated_one(x, y, kernel, blur):
     return loss_from(mats), gx, gy
 
 
+def grads_from(mats, kernel, blur, keep=None):
+    """(grad_x, grad_y) in float64 from pair_matrices' result, restated_one's formula.  keep = (mask over x's
+    points, mask over y's): every point's sums run over those columns only -- what a kernel that dropped a
+    tile of columns would compute (loss_from's skip_cols, for the gradients)."""
+    x, y, (_, gxx), (_, gyy), (_, gxy) = mats
+    a, b = 1.0 / len(x), 1.0 / len(y)
+    C = derivative_factor(kernel, float(np.float32(blur)))
+    kx, ky = (np.ones(len(x), bool), np.ones(len(y), bool)) if keep is None else keep
+
+    def v(p, g, q):  # sum_q g (p - q)
+        return p * g.sum(1)[:, None] - g @ q
+
+    gx = C * a * (a * v(x, gxx[:, kx], x[kx]) - b * v(x, gxy[:, ky], y[ky]))
+    gy = C * b * (b * v(y, gyy[:, ky], y[ky]) - a * v(y, gxy.T[:, kx], x[kx]))
+    return gx, gy
+
+
 @functools.lru_cache(maxsize=None)
 def restated(b, n, m, kernel, blur, seed=0):
     """(L [b], grad_x [b, n, 3], grad_y [b, m, 3]) of make_clouds(b, n, m, seed), computed once."""
