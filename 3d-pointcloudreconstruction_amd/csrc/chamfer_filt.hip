@@ -792,8 +792,10 @@ __device__ __forceinline__ float filt_forward(const TIn *__restrict__ Q, const T
 // (every wave loads the 256 queries and reduces the centre itself), the next
 // group's A tiles read a group ahead, the lane groups folded in registers,
 // the merge of the four quarters, the proof and the exact rescan in one pass
-// by (query, part) threads, near ties listed with a plan and rescanned by one
-// wave each over the planned chunks only, and the per-query bound: E above
+// by (query, part) threads, near ties rescanned over their plan's chunks only
+// by the two waves that hold the query (no list, no second barrier: the
+// query, its plan and its chunks come from registers by v_readlane, and a
+// wave's near ties alternate between the two parts), and the per-query bound: E above
 // with (R + |q'|)^2 replaced by min((R + |q'|)^2, (2|q'| + sqrt(d_b))^2), by
 // filt_forward's argument.  Fused variants 6 and 19.
 //
@@ -923,17 +925,14 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     float(*sPB)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4);
     float(*sPS)[QW] = reinterpret_cast<float(*)[QW]>(arena + 3 * TILE * 4 + 4 * QW * 4);
     int(*sPC)[QW] = reinterpret_cast<int(*)[QW]>(arena + 3 * TILE * 4 + 8 * QW * 4);
-    float(*sQR)[QW] = reinterpret_cast<float(*)[QW]>(arena + MfmaLds::kTail);  // raw queries (after the scan)
-    static_assert(MfmaLds::kTail + 3 * QW * 4 <= MfmaLds::kBytes, "raw queries fit the arena behind the partials");
-    __shared__ float sD[QW];  // near-tie results
-    __shared__ int sK[QW];
-    __shared__ unsigned sPlan[QW];
-    __shared__ float sHD[2][QW];
+    __shared__ float sHD[2][QW];  // each part's exact (distance, index) of the query
     __shared__ int sHK[2][QW];
     __shared__ float sRmax[W];
-    __shared__ int sList[QW];
-    __shared__ int sNList;
     __shared__ int sNFm[W];
+#ifdef PCM_STAMPS
+    __shared__ unsigned sCensus[4];  // near ties, whole quarters, single chunks, most iterations of a wave
+    if (threadIdx.x < 4) sCensus[threadIdx.x] = 0;  // first touched after the staging barrier
+#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -968,7 +967,6 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
             ++qcnt;
         }
     }
-    if (tid == 0) sNList = 0;  // first read after the staging barrier
     // every wave reduces the centre itself (same instructions, same bits): no barrier
     const float cn = (float)wave_sum_dpp(qcnt);
     const float c0 = wave_sum_dpp(cx) / cn, c1 = wave_sum_dpp(cy) / cn, c2 = wave_sum_dpp(cz) / cn;
@@ -1255,10 +1253,6 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
         const int p = tid + r * NT;
         if (p < nt) { sT[0][mslot(p)] = tv[r][0]; sT[1][mslot(p)] = tv[r][1]; sT[2][mslot(p)] = tv[r][2]; }
     }
-    // and the raw queries for the near-tie pass (thread tid < QW holds query
-    // tid): the per-wave register copies rx, ry, rz end at the query split, so
-    // the screen loop does not carry them
-    if (tid < QW) { sQR[0][tid] = qx; sQR[1][tid] = qy; sQR[2][tid] = qz; }
     // the four lane groups of a wave hold the same 8 query tiles against
     // different chunks: two halving steps leave lane group g with the folded
     // partials of tiles 4 (g >> 1) + 2 (g & 1) + {0, 1}; one partial per
@@ -1299,12 +1293,12 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
     if (!any_nonfinite) {
         // ---- one pass, one barrier: thread (s = tid mod QW, part = tid / QW)
         // merges the four quarters' partials of query s -- both parts reach
-        // the same verdict -- and, when the best chunk is proven, rescans its
-        // half of that chunk exactly (tiles 2 part, 2 part + 1 of the group,
-        // rows 4g..4g+3, ascending); part 0 of a near-tie query lists it with
-        // its plan instead.
+        // the same verdict and the same plan -- and, when the best chunk is
+        // proven, rescans its half of that chunk exactly (tiles 2 part,
+        // 2 part + 1 of the group, rows 4g..4g+3, ascending).  A wave then
+        // scans the near ties among its 64 queries itself, in turn with the
+        // other part's wave.
         const int s = tid & (QW - 1), part = tid / QW;
-        bool proven = false;
         {
             float vb[4], vs[4], vr[W];
             int vc[4];
@@ -1341,10 +1335,20 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
             const float db = __builtin_fmaxf((fb + qn2) * 1.0001f + 2.f * eR, 0.f);
             const float rq = 2.f * sq + __builtin_amdgcn_sqrtf(db);
             const float e2 = 2.f * (kFiltU80 * __builtin_fminf(rr * rr, rq * rq) * 1.001f + kAbs);
-            proven = (fs - fb) > e2;  // false for NaN
+            const bool proven = (fs - fb) > e2;  // false for NaN
+            const bool live = qbase + s < nq;
+            // near-tie plan: quarter q is scanned whole (bit q) when its
+            // second-best chunk may lie within fb + 2E, else its best chunk
+            // alone (bit 4 + q) when that one may; every other candidate
+            // screens above fb + 2E, so lies above the answer.  NaN anywhere
+            // selects the scan.
+            const float thr = fb + e2;
+            unsigned plan = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) plan |= !(vs[q] > thr) ? (1u << q) : (!(vb[q] > thr) ? (16u << q) : 0u);
             float hd = PCM_INF;
             int hk = 0x7fffffff;
-            if (qbase + s < nq) {
+            if (live) {
                 if (proven) {
                     // two quads of the raw tile, 16 targets apart; a quad stays
                     // contiguous under mslot, and slots past nt (inside the last
@@ -1371,97 +1375,109 @@ __device__ __forceinline__ float filt_forward_mfma(const float *__restrict__ Q, 
                         hd = take ? d : hd;
                         hk = take ? kk : hk;
                     }
-                } else if (part == 0) {
-                    // near-tie plan: quarter q is scanned whole (bit q) when its
-                    // second-best chunk may lie within fb + 2E, else its best
-                    // chunk alone (bit 4 + q) when that one may; every other
-                    // candidate screens above fb + 2E, so lies above the
-                    // answer.  NaN anywhere selects the scan.
-                    const float thr = fb + e2;
-                    unsigned plan = 0;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) plan |= !(vs[q] > thr) ? (1u << q) : (!(vb[q] > thr) ? (16u << q) : 0u);
-                    sPlan[s] = plan;
-                    sList[atomicAdd(&sNList, 1)] = s;
                 }
+            }
+            PCM_STAMP(5);
+            // ---- near ties, inside the wave that holds the query: waves w
+            // and w + 4 hold the same 64 queries (parts 0 and 1) and see the
+            // same mask; its j-th set bit falls to part j & 1, whose wave
+            // scans that query's whole plan exactly and hands the result to
+            // the query's own lane, while the other part keeps (+inf, none):
+            // the outputs take the lexmin of the two parts, as for a proven
+            // query.  The query, its plan and its quarters' best chunks come
+            // from the listed lane's registers.  One step takes the four
+            // quarters' single chunks (lane group q: the 16 targets of quarter
+            // q's best chunk); a whole quarter is its up to four 64-target
+            // groups, one target per lane each.
+            unsigned long long todo = __builtin_amdgcn_ballot_w64(live && !proven);
+            const int wpart = wave / QPT;  // this wave's part, wave-uniform
+#ifdef PCM_STAMPS
+            {  // census (each query once: the part-0 waves count) and this wave's iterations
+                const bool on = live && !proven && wpart == 0;
+                const int nfull = wave_sum_dpp(on ? (int)__popc(plan & 15u) : 0);
+                const int nsingle = wave_sum_dpp(on ? (int)__popc((plan >> 4) & 15u) : 0);
+                if (lane == 0) {
+                    const unsigned cnt = (unsigned)__popcll(todo);
+                    if (wpart == 0) {
+                        atomicAdd(&sCensus[0], cnt);
+                        atomicAdd(&sCensus[1], (unsigned)nfull);
+                        atomicAdd(&sCensus[2], (unsigned)nsingle);
+                    }
+                    atomicMax(&sCensus[3], (cnt + 1u - (unsigned)wpart) >> 1);
+                }
+            }
+#endif
+            for (int j = 0; todo != 0; ++j) {
+                const int l = __builtin_ctzll(todo);
+                todo &= todo - 1;
+                if ((j & 1) != wpart) continue;
+                // (the lane, opaque per iteration: from a loop-invariant lane
+                // hipcc computes all sixteen whole-quarter slots and masks
+                // ahead of the loop -- 270 instructions and SGPR spills, 0.7 us
+                // in every wave that holds a near tie, most of which scan no
+                // whole quarter; section 3.5c)
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                const float x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qx), l));
+                const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qy), l));
+                const float z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz), l));
+                const unsigned pl = (unsigned)__builtin_amdgcn_readlane((int)plan, l);
+                float bd = PCM_INF;
+                int bk = 0x7fffffff;
+                {
+                    const int p0 = __builtin_amdgcn_readlane(vc[0], l), p1 = __builtin_amdgcn_readlane(vc[1], l);
+                    const int p2 = __builtin_amdgcn_readlane(vc[2], l), p3 = __builtin_amdgcn_readlane(vc[3], l);
+                    const int pc = g == 0 ? p0 : g == 1 ? p1 : g == 2 ? p2 : p3;
+                    const int k = kWide ? 64 * (pc >> 2) + 32 * ((pc >> 1) & 1) + 4 * (pc & 1) + 8 * (col >> 2) + (col & 3)
+                                        : 64 * (pc >> 2) + 16 * (col >> 2) + 4 * (pc & 3) + (col & 3);
+                    const bool on = ((pl >> (4 + g)) & 1u) && k < nt;
+                    const int ks = mslot(min(k, nt - 1));
+                    const float d = pcm_sqd(sT[0][ks] - x, sT[1][ks] - y, sT[2][ks] - z);
+                    if (on) pcm_lexmin(bd, bk, d, k);
+                }
+                for (int q = 0; q < 4; ++q) {
+                    if (!((pl >> q) & 1u)) continue;
+                    float tx[4], ty[4], tz[4];
+                    int kk[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {  // the quarter's groups, all loads in flight
+                        const int k = 64 * (q + 4 * u) + ln;
+                        // (the group from k: not a mask per (q, u) kept across the loop)
+                        kk[u] = ((k >> 6) < ngroups && k < nt) ? k : -1;
+                        const int ks = mslot(min(max(kk[u], 0), nt - 1));
+                        tx[u] = sT[0][ks];
+                        ty[u] = sT[1][ks];
+                        tz[u] = sT[2][ks];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float d = pcm_sqd(tx[u] - x, ty[u] - y, tz[u] - z);
+                        if (kk[u] >= 0) pcm_lexmin(bd, bk, d, kk[u]);
+                    }
+                }
+                pcm_wave_lexmin(bd, bk);
+                hd = lane == l ? bd : hd;
+                hk = lane == l ? bk : hk;
             }
             sHD[part][s] = hd;
             sHK[part][s] = hk;
         }
         __syncthreads();
-        PCM_STAMP(5);
-        // ---- near-ties: one wave per listed query, exact scan of the plan's
-        // candidates only.  One step takes the four quarters' single chunks
-        // (lane group q: the 16 targets of quarter q's best chunk); a whole
-        // quarter is its up to four 64-target groups, one target per lane each.
-        const int nl = sNList;
-        for (int e = wave; e < nl; e += W) {
-            const int sq = __builtin_amdgcn_readfirstlane(sList[e]);
-            const unsigned plan = __builtin_amdgcn_readfirstlane(sPlan[sq]);
-            // sq is wave-uniform: one broadcast read each, beside the plan's
-            const float x = sQR[0][sq], y = sQR[1][sq], z = sQR[2][sq];
-            float bd = PCM_INF;
-            int bk = 0x7fffffff;
-            {
-                const int pc = sPC[g][sq];
-                const int k = kWide ? 64 * (pc >> 2) + 32 * ((pc >> 1) & 1) + 4 * (pc & 1) + 8 * (col >> 2) + (col & 3)
-                                    : 64 * (pc >> 2) + 16 * (col >> 2) + 4 * (pc & 3) + (col & 3);
-                const bool on = ((plan >> (4 + g)) & 1u) && k < nt;
-                const int ks = mslot(min(k, nt - 1));
-                const float d = pcm_sqd(sT[0][ks] - x, sT[1][ks] - y, sT[2][ks] - z);
-                if (on) pcm_lexmin(bd, bk, d, k);
-            }
-            for (int q = 0; q < 4; ++q) {
-                if (!((plan >> q) & 1u)) continue;
-                float tx[4], ty[4], tz[4];
-                int kk[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {  // the quarter's groups, all loads in flight
-                    const int k = 64 * (q + 4 * u) + lane;
-                    kk[u] = (q + 4 * u < ngroups && k < nt) ? k : -1;
-                    const int ks = mslot(min(max(kk[u], 0), nt - 1));
-                    tx[u] = sT[0][ks];
-                    ty[u] = sT[1][ks];
-                    tz[u] = sT[2][ks];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float d = pcm_sqd(tx[u] - x, ty[u] - y, tz[u] - z);
-                    if (kk[u] >= 0) pcm_lexmin(bd, bk, d, kk[u]);
-                }
-            }
-            pcm_wave_lexmin(bd, bk);
-            if (lane == 0) {
-                sD[sq] = bd;
-                sK[sq] = bk;
-            }
-        }
-        if (nl > 0) __syncthreads();
         PCM_STAMP(6);
 #ifdef PCM_STAMPS
         if (tid == 0 && blockIdx.x < 4096) g_pcm_stamps[(8192 + blockIdx.x) * 8 + 6] = __builtin_amdgcn_s_memtime();
-        if (tid == NT - 1 && blockIdx.x < kStampSlots) {  // diagnostics: ties, whole quarters, single chunks
-            unsigned long long full = 0, single = 0;
-            for (int e = 0; e < nl; ++e) {
-                const unsigned pl = sPlan[sList[e]];
-                full += __popc(pl & 15);
-                single += __popc((pl >> 4) & 15);
-            }
-            g_pcm_stamps[blockIdx.x * 8 + 0] = (unsigned long long)nl | (full << 16) | (single << 40);
-        }
+        // diagnostics: near ties (bits 0-15), whole quarters (16-31), the most
+        // loop iterations of one wave (32-39), single chunks (40 up)
+        if (tid == NT - 1 && blockIdx.x < kStampSlots)
+            g_pcm_stamps[blockIdx.x * 8 + 0] = (unsigned long long)sCensus[0] | ((unsigned long long)sCensus[1] << 16) |
+                                               ((unsigned long long)sCensus[3] << 32) |
+                                               ((unsigned long long)sCensus[2] << 40);
 #endif
-        // ---- outputs (thread tid < QW is part 0 of query tid: `proven` is that query's verdict)
+        // ---- outputs (thread tid < QW is part 0 of query tid): the nearer of the two parts' results
         if (tid < QW && qbase + tid < nq) {
-            float d;
-            int k;
-            if (proven) {
-                d = sHD[0][tid];
-                k = sHK[0][tid];
-                pcm_lexmin(d, k, sHD[1][tid], sHK[1][tid]);
-            } else {
-                d = sD[tid];
-                k = sK[tid];
-            }
+            float d = sHD[0][tid];
+            int k = sHK[0][tid];
+            pcm_lexmin(d, k, sHD[1][tid], sHK[1][tid]);
             my_d = d;
             out_st<kSc1>(D + qbase + tid, d);
             out_st<kSc1>(I + qbase + tid, (int32_t)k);

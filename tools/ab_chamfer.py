@@ -26,6 +26,11 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(1234)
     x1 = torch.rand(b, n, 3, generator=g).to(dev)
     x2 = torch.rand(b, m, 3, generator=g).to(dev)
+    if os.environ.get("AB_CLOUDS") == "collapsed":
+        # the near-tie pass's worst case: every cloud one point, so every
+        # chunk ties with every other and every query scans four whole quarters
+        x1 = x1[:, :1].expand(b, n, 3).contiguous()
+        x2 = x2[:, :1].expand(b, m, 3).contiguous()
     d1, d2 = torch.empty(b, n, device=dev), torch.empty(b, m, device=dev)
     i1 = torch.empty(b, n, dtype=torch.int32, device=dev)
     i2 = torch.empty(b, m, dtype=torch.int32, device=dev)

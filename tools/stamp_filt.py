@@ -5,7 +5,10 @@ Needs the profiling build (make -C 3d-pointcloudreconstruction_amd/csrc stamps),
 loaded through PCM_HIP_LIB.  Thread 0 of every workgroup records
 s_memrealtime (100 MHz) at: 0 start, 1 centre barrier, 2 first tile staged,
 3 scan done, 4 merge/proof done, 5 rescan done, 6 near-tie scans done,
-7 end.
+7 end.  In the matrix-core forward (fused variants 6, 19, 20) stamp 5 stands
+behind the exact rescan of thread 0's wave, ahead of that wave's near-tie
+loop, and stamp 6 behind the one barrier that follows the loop: "ties" is the
+loop of wave 0 plus its wait for the workgroup's slowest wave.
 
     python tools/stamp_filt.py VARIANT [VARIANT ...]
     python tools/stamp_filt.py fused [VARIANT ...]     (pcm_chamfer_loss_grad)
@@ -132,12 +135,16 @@ def run_fused(v, b, n, m, dev):
     # the forward's own stamps (table's lower half, same workgroup numbering)
     lo = [[buf[i * 8 + k] for k in range(8)] for i in range(nblk - 1)]
     if v in (6, 19, 20):  # the matrix-core forward stores its near-tie census in slot 0
+        # bits 0-15 near ties, 16-31 whole quarters, 32-39 the most near-tie
+        # loop iterations any one wave ran, 40 up single chunks
         nl = [r[0] & 0xffff for r in lo]
-        full = sum((r[0] >> 16) & 0xffffff for r in lo)
+        full = sum((r[0] >> 16) & 0xffff for r in lo)
+        iters = [(r[0] >> 32) & 0xff for r in lo]
         single = sum(r[0] >> 40 for r in lo)
         print(f"  near-ties per workgroup: median {statistics.median(nl)} max {max(nl)} total {sum(nl)} "
               f"({100.0 * sum(nl) / (64 * FUSED_QPT[v] * len(lo)):.2f}% of queries); whole quarters {full}, "
-              f"single chunks {single}")
+              f"single chunks {single}; most loop iterations of one wave: median {statistics.median(iters)} "
+              f"max {max(iters)}")
         cyc = [[buf[(8192 + i) * 8 + k] for k in range(8)] for i in range(nblk - 1)]
         ghz = [(c[6] - c[1]) / ((r[6] - r[1]) * 10.0) for c, r in zip(cyc, lo) if r[6] > r[1]]
         print(f"  shader clock over stamps 1..6: median {statistics.median(ghz):.2f} GHz, "
