@@ -350,7 +350,8 @@ int pcm_chamfer_eval_f16(const uint16_t *xyz1, const uint16_t *xyz2, int b, int 
  *   (autograd's backward of the sum above).  Order: per row h the columns in
  *   slices of eight (pairwise inside a slice), rows ascending, then the slices
  *   ascending; it depends on the grid alone.  Fully overwritten, no atomics.
- *   Its result for non-finite coordinates is unspecified.
+ *   Its result for a point with a non-finite coordinate is unspecified for
+ *   that point; all other points are unaffected.
  * layout: 0 = [b, n, 3] rows, 1 = [b, 3, n] channel planes, as
  *   pcm_chamfer_forward_layout: read in place, and gradxyz is written in the
  *   same layout.  perspective_transform returns such a view of planes

@@ -1,6 +1,7 @@
 """Inputs outside the unit cube and on degenerate geometry for the newer losses
 (kNN / repulsion, FPS, ball query, the uniform loss, the kernel norms, Sinkhorn,
-sliced Wasserstein, DCD).
+sliced Wasserstein, DCD) and for the ninth op, the one-pass Chamfer evaluation
+behind fscore (csrc/chamfer_eval.hip).
 
 Shared by tests/test_geometry_cpu.py (which keeps the inputs, the restatements
 and the bounds honest on these clouds) and tests/test_geometry_gpu.py (the HIP
@@ -47,11 +48,14 @@ kept.  Ops that take one cloud use x.  What each family moves:
     the one DCD term with alpha d far above 16000.
   * scale_2e5 (FPS only): squared distances above kFpsFar = 1e10f, so running
     minima stay saturated and the next seed is the lowest saturated index.
-  * scale_1e-20 (FPS, ball query): every squared distance is a float32
+  * scale_1e-20 (FPS, ball query, F-score): every squared distance is a float32
     subnormal, which `d < run`, the wave maximum (sampling.hip: "float32
-    denormals preserved") and `d < sc.r2[q]` must keep.
-  * offset_duplicates (duplicates, then + 1000; kNN, repulsion, FPS and the
-    ball query -- not in the issue's table): what offset_1000 alone cannot
+    denormals preserved"), `d < sc.r2[q]` and, in chamfer_eval.hip, the packed
+    fp32 scan (pcm_sqd2), its running minimum and the `d < th.v[t]` ballots
+    must keep; the F-score thresholds go with s^2, so the first three are
+    subnormal themselves (1e-44, 1e-43, 1e-42).
+  * offset_duplicates (duplicates, then + 1000; kNN, repulsion, FPS, the
+    ball query and F-score -- not in the issue's table): what offset_1000 alone cannot
     have in three dimensions, at coordinate 1000: d = 0 between distinct
     indices (the self search's slot 1, FPS minima) and exact ties inside a
     list.
@@ -60,6 +64,10 @@ the two-cloud ops.  For the ball query x is the centres and y the cloud they
 search: collapsed gives 65 equal centres (every ball the same list), identical
 searches the centres themselves, so every ball holds its own centre at d = 0
 and none is empty (the one family exempt from the three-kinds assertion).
+The F-score op takes seeded uniform clouds as kNN does; its shapes take 2 queries
+per lane (eval_qpt), the second with one direction exactly on the 2048-candidate
+LDS tile and the other one below it.  Its thresholds are FSCORE_THS times s^2
+rounded to float32, its reference the oracle's chamfer_forward.
 Non-finite coordinates (every op has a test for them) and magnitudes at which
 a float32 squared distance overflows are out of scope.
 """
@@ -160,7 +168,7 @@ FAMILIES = {
     "fps": ONE_CLOUD + ("scale_2e5", "scale_1e-20", "offset_duplicates"),
     "ball": GENERAL + ("scale_1e-20", "offset_duplicates"),
     "uniform": ONE_CLOUD, "kernel": GENERAL, "sinkhorn": tuple(f for f in GENERAL if f != "bimodal"),
-    "sliced": GENERAL, "dcd": GENERAL,
+    "sliced": GENERAL, "dcd": GENERAL, "fscore": GENERAL + ("scale_1e-20", "offset_duplicates"),
 }
 # Sinkhorn leaves out `bimodal`: its diameter is 1001 while the transport is between unit-size halves, so the
 # tolerances scaled by D (0.33 on a loss of 14, 0.058 on n |grad| of 0.8) are wider than what a left-out schedule
@@ -179,8 +187,10 @@ SHAPES = {
     "knn": [(2, 300, 1025)], "repulsion": [(2, 300, 300)], "fps": [(2, 300, 20), (2, 1025, 33)],
     "ball": [(2, 65, 257)], "uniform": [(2, 300, 300)], "kernel": [(2, 257, 255), (2, 300, 1025)],
     "sinkhorn": [(2, 127, 128), (2, 300, 1025)], "sliced": [(2, 1000, 333, 65), (2, 1025, 1025, 3)],
-    "dcd": [(2, 1000, 333), (2, 1025, 1023)],
+    "dcd": [(2, 1000, 333), (2, 1025, 1023)], "fscore": [(2, 300, 1025), (2, 2048, 2047)],
 }
+FSCORE_WIDE_SHAPE = (64, 1030, 700)  # the 4-queries-per-lane kernel: `centred` and `offset_1000` only
+FSCORE_THS = (1e-4, 1e-3, 1e-2, 1.0, 30.0)
 KNN_KS = (5, 20)
 REPULSION_H = 0.01
 BALL_NSAMPLE, BALL_RADII = 12, (0.05, 0.3)
@@ -191,7 +201,7 @@ DCD_LAMBDAS = (1.0, 0.5)
 
 
 def _base(op, b, n, m):
-    if op in ("knn", "repulsion"):
+    if op in ("knn", "repulsion", "fscore"):
         rng = np.random.default_rng(4100 + 7 * n + m)
         return rng.random((b, n, 3), dtype=F32), rng.random((b, m, 3), dtype=F32)
     if op == "fps":
@@ -353,6 +363,23 @@ def dcd_forward(family, shape):
         alpha = dcd_forward("unit", shape)[4]
     assert np.isfinite(alpha) and alpha > 0
     return d1, d2, i1, i2, alpha
+
+
+def fscore_thresholds(c):
+    """FSCORE_THS times s^2, rounded to float32 (as Python floats: what the call takes)."""
+    return tuple(float(F32(t * c.s * c.s)) for t in FSCORE_THS)
+
+
+@functools.lru_cache(maxsize=None)
+def fscore_forward(family, shape):
+    """(d1, d2): the oracle's nearest squared distances of the case, read-only."""
+    import oracle as O
+    O.build()
+    c = case("fscore", family, shape)
+    d1, d2, _, _ = O.chamfer_forward(c.x, c.y)
+    d1.setflags(write=False)
+    d2.setflags(write=False)
+    return d1, d2
 
 
 @functools.lru_cache(maxsize=None)

@@ -20,6 +20,11 @@ import numpy as np
 import pytest
 import torch
 
+from fscore_restated import batch_from as _batch_from
+from fscore_restated import bits as _bits
+from fscore_restated import counts_from as _counts_from
+from fscore_restated import scores_from as _scores_from
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fscore_golden.npz")
@@ -51,33 +56,6 @@ def _run(cuda, a, c, ths, workspace=None, with_batch=True):
     return (md.cpu().numpy(), cn.cpu().numpy(), sc.cpu().numpy(), bs.cpu().numpy() if with_batch else None)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x).view(np.int32)
-
-
-def _counts_from(d, ths):
-    """[B, T] counts of d [B, P] (float32) strictly under each float32 threshold."""
-    th = np.asarray(ths, np.float32)
-    return (d[:, None, :] < th[None, :, None]).sum(-1).astype(np.int32)
-
-
-def _scores_from(c1, c2, n, m):
-    """The pinned arithmetic of include/pcm.h in float32."""
-    p_x = c1.astype(np.float32) / np.float32(n)
-    p_y = c2.astype(np.float32) / np.float32(m)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        f = ((np.float32(2) * p_y) * p_x) / (p_y + p_x)
-    f = np.where(c1 + c2 == 0, np.float32(0), f).astype(np.float32)
-    return np.stack([f, p_x, p_y], -1)
-
-
-def _batch_from(scores):
-    s = np.zeros(scores.shape[1:], np.float32)
-    for i in range(scores.shape[0]):  # sequential, ascending b
-        s = s + scores[i]
-    return s / np.float32(scores.shape[0])
-
-
 # ---- reference parity ---------------------------------------------------------
 
 @pytest.mark.parametrize("case", _golden_cases())
@@ -105,10 +83,11 @@ def test_reference_parity_on_the_fixture(cuda, case):
 # ---- oracle and product parity ------------------------------------------------
 
 # (b, n, m): single points; tiny ragged; under one wave; across the 2048-point
-# LDS tile; config 2's cloud; config 2; ragged multi-block; and the two sides
-# of the 2- / 4-queries-per-lane switch (512 workgroups of 256 queries)
+# LDS tile; config 2's cloud; config 2; ragged multi-block; the two sides
+# of the 2- / 4-queries-per-lane switch (512 workgroups of 256 queries); and
+# exactly one and exactly two LDS tiles (no padded chunk, no partial tile)
 SHAPES = [(1, 1, 1), (2, 5, 3), (2, 33, 31), (1, 2049, 2047), (3, 1024, 1024), (32, 1024, 1024), (2, 5000, 700),
-          (255, 70, 50), (256, 70, 50), (64, 1030, 700)]
+          (255, 70, 50), (256, 70, 50), (64, 1030, 700), (1, 2048, 2048), (1, 4096, 2048)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -258,6 +237,24 @@ def test_fp16_equals_fp32_on_widened_clouds(cuda, shape):
     half = _run(cuda, a, c, THS)
     wide = _run(cuda, a.float(), c.float(), THS)
     assert half[1][:, 2].sum() > 0  # fp16 clouds are coarse, but the counts are not trivially empty
+    for h, w in zip(half, wide):
+        np.testing.assert_array_equal(_bits(h), _bits(w))
+
+
+def test_fp16_non_finite_equals_fp32_on_widened_clouds(cuda):
+    # a NaN at a tile start of xyz2 and a +inf in mid-cloud of xyz1, both in batch element 0: its workgroups
+    # divert to the reference-exact scan in either entry; batch element 1 stays finite
+    g = torch.Generator().manual_seed(33)
+    a, c = torch.rand(2, 2100, 3, generator=g).half(), torch.rand(2, 2100, 3, generator=g).half()
+    c[0, 2048, 0] = float("nan")
+    a[0, 700, 2] = float("inf")
+    assert torch.isfinite(a[1]).all() and torch.isfinite(c[1]).all()
+    ths = (1e-4, 1e-3, 1e-2, float("inf"))
+    half = _run(cuda, a, c, ths)
+    wide = _run(cuda, a.float(), c.float(), ths)
+    assert 0 < half[1][1, 2].sum() and half[1][1, 3].tolist() == [2100, 2100]
+    assert half[1][0, 3].sum() < 4200  # the non-finite points do reach the counts of element 0
+    assert np.isfinite(half[0][1]).all()
     for h, w in zip(half, wide):
         np.testing.assert_array_equal(_bits(h), _bits(w))
 

@@ -3,11 +3,14 @@ row of the table claims (on the restatement), the float32 restatements stay
 inside the bounds the GPU comparison uses on every case, the modelled defects
 of each module still leave those bounds, the two assumptions behind
 kernel_loss_restated.grad_bound and dcd_restated's RHO hold or are covered,
-and scaling by 1024 keeps the index outputs bit for bit."""
+scaling by 1024 keeps the index outputs bit for bit, and the ninth op's
+(F-score: the one-pass Chamfer evaluation) thresholds separate the points of
+every family, across subnormal distances and exact ties where the table says so."""
 import numpy as np
 import pytest
 
 import dcd_restated as D
+import fscore_restated as FS
 import geometry_cases as G
 import kernel_loss_restated as K
 import sinkhorn_restated as S
@@ -29,7 +32,8 @@ def test_every_op_takes_the_families_of_the_table():
     for op, families in G.FAMILIES.items():
         assert set(G.GENERAL) - {"identical", "far_point", "bimodal"} <= set(families)
         assert set(families) <= set(G.GENERAL) | {"scale_2e5", "scale_1e-20", "offset_duplicates"}
-        assert ("scale_2e5" in families) == (op == "fps") and ("scale_1e-20" in families) == (op in ("fps", "ball"))
+        assert ("scale_2e5" in families) == (op == "fps")
+        assert ("scale_1e-20" in families) == (op in ("fps", "ball", "fscore"))
     for op in G.FAMILIES:
         for family, shape in G.entries(op):
             c, u = G.case(op, family, shape), G.case(op, "unit", shape)
@@ -157,6 +161,87 @@ def test_scaled_parameters_go_with_the_cloud():
     assert G.diameter(G.case("sinkhorn", "scale_1e-3", (2, 127, 128))) == pytest.approx(1e-3 * S.DIAMETER, rel=1e-6)
     c = G.case("sinkhorn", "far_point", (2, 127, 128))
     assert G.diameter(c) == float(np.float32(K.diameter(c.x, c.y))) > 50
+
+
+# ---------------------------------------------------------------------------
+# F-score: the thresholds separate the points
+# ---------------------------------------------------------------------------
+# `identical`: every nearest distance is 0, under every positive threshold -- all counts full (asserted).
+# `line`: 300 and 1025 points on one segment of length 1 are at most 2e-3 apart, squared 4e-6 < 1e-4 (but for a
+# point or two past the other cloud's ends) -- the counts are full or one short at every threshold (asserted).
+FSCORE_TRIVIAL = ("identical", "line")
+
+
+def test_fscore_thresholds_separate_the_points_of_every_family(oracle):
+    """Per family and shape the counts over the five thresholds are neither all 0 nor all full in either
+    direction, and the five (count1, count2) pairs hold three distinct ones, for every family but FSCORE_TRIVIAL."""
+    assert set(G.FAMILIES["fscore"]) == set(G.GENERAL) | {"scale_1e-20", "offset_duplicates"}
+    assert G.SHAPES["fscore"] == [(2, 300, 1025), (2, 2048, 2047)]  # 2 queries per lane; on and one below the tile
+    for family, shape in G.entries("fscore"):
+        c = G.case("fscore", family, shape)
+        b, n, m = shape[0], c.x.shape[1], c.y.shape[1]
+        th = G.fscore_thresholds(c)
+        assert len(th) == 5 and all(np.float32(t) == t and t > 0 for t in th)
+        d1, d2 = G.fscore_forward(family, shape)
+        assert d1.shape == (b, n) and d2.shape == (b, m) and d1.dtype == np.float32
+        c1, c2 = FS.counts_from(d1, th).sum(0), FS.counts_from(d2, th).sum(0)
+        print(family, shape, c1.tolist(), c2.tolist())
+        if family == "identical":
+            assert not d1.any() and not d2.any() and (c1 == b * n).all() and (c2 == b * m).all()
+        elif family == "line":
+            assert (c1 >= b * n - 2).all() and (c2 >= b * m - 2).all()
+        else:
+            for cnt, full in ((c1, b * n), (c2, b * m)):
+                assert not (cnt == 0).all() and not (cnt == full).all(), (family, shape)
+                assert len(np.unique(cnt)) >= 2, (family, shape, cnt)
+            # three distinct (count1, count2) pairs: `collapsed` has two values in its first direction alone
+            assert len(set(zip(c1.tolist(), c2.tolist()))) >= 3, (family, shape)
+    for family in ("centred", "offset_1000"):  # the 4-queries-per-lane case
+        c = G.case("fscore", family, G.FSCORE_WIDE_SHAPE)
+        assert c.x.shape == (64, 1030, 3) and c.y.shape == (64, 700, 3)
+        assert 64 * ((1030 + 255) // 256 + (700 + 255) // 256) >= 512  # eval_qpt's switch
+
+
+def test_fscore_subnormal_distances_straddle_subnormal_thresholds(oracle):
+    """scale_1e-20: every nearest distance is a float32 subnormal (or 0), the first three thresholds are
+    subnormal, and at least two thresholds have subnormal distances on both sides."""
+    for shape in G.SHAPES["fscore"]:
+        c = G.case("fscore", "scale_1e-20", shape)
+        th = np.float32(G.fscore_thresholds(c))
+        assert (th[:3] < TINY).all() and (th > 0).all() and th[4] < TINY
+        d = np.concatenate([v.ravel() for v in G.fscore_forward("scale_1e-20", shape)])
+        sub = (d > 0) & (d < TINY)
+        print(shape, "subnormal", int(sub.sum()), "zero", int((d == 0).sum()), "of", d.size)
+        assert (d < TINY).all() and sub.sum() >= d.size - 2
+        straddled = [t for t in th if (d[sub] < t).any() and (d[sub] >= t).any()]
+        assert len(straddled) >= 2, straddled
+        # subnormals are multiples of 2^-149 and the first threshold is 7 of them: distances bit-equal to a
+        # threshold exist, and the strict count leaves them out
+        d1 = G.fscore_forward("scale_1e-20", shape)[0]
+        equal = (d1[:, None, :] == th[None, :, None]).sum(-1)
+        assert equal[:, :3].sum() >= 1, equal
+        assert np.array_equal(FS.counts_from(d1, th), d1.shape[1] - (d1[:, None, :] >= th[None, :, None]).sum(-1))
+        # the counts are the unit pair's but for the quantisation of a subnormal: they move by a few points
+        unit = G.case("fscore", "unit", shape)
+        want = FS.counts_from(G.fscore_forward("unit", shape)[0], G.fscore_thresholds(unit)).sum(0)
+        got = FS.counts_from(G.fscore_forward("scale_1e-20", shape)[0], th).sum(0)
+        assert np.abs(got - want).max() <= 0.02 * d.size and (got[3:] == want[3:]).all()
+
+
+def test_fscore_offset_cloud_has_bit_equal_candidates(oracle):
+    """offset_1000: coordinates quantised to 2^-14, so a query meets distinct candidates at bit-equal pinned
+    distances; the scan's minimum does not depend on which of them it meets first.  offset_duplicates: the
+    nearest distance itself is attained twice."""
+    shape = G.SHAPES["fscore"][0]
+    c = G.case("fscore", "offset_1000", shape)
+    diff = c.y[0][None, :, :] - c.x[0][:, None, :]
+    d = np.sort(U.sqd_pinned(diff[..., 0], diff[..., 1], diff[..., 2]), axis=1)
+    assert (d[:, 1:] == d[:, :-1]).any(axis=1).sum() >= 2
+    assert np.array_equal(d[:, 0].view(np.int32), G.fscore_forward("offset_1000", shape)[0][0].view(np.int32))
+    c = G.case("fscore", "offset_duplicates", shape)
+    diff = c.y[0][None, :, :] - c.x[0][:, None, :]
+    d = np.sort(U.sqd_pinned(diff[..., 0], diff[..., 1], diff[..., 2]), axis=1)
+    assert (d[:, 0] == d[:, 1]).sum() >= 0.9 * d.shape[0]
 
 
 # ---------------------------------------------------------------------------

@@ -5,7 +5,10 @@ groups EQUAL to the restatement; pcm_repulsion_loss, pcm_uniform_loss,
 pcm_kernel_loss, pcm_sinkhorn_loss, pcm_sliced_wasserstein_loss and
 pcm_dcd_loss within the modules' own derived bounds evaluated on the case
 (Sinkhorn: the tolerances of geometry_cases.sinkhorn_reference, which
-tests/test_geometry_cpu.py holds between its two conditions).  Every case is
+tests/test_geometry_cpu.py holds between its two conditions); and the ninth
+op, pcm_chamfer_eval (the one-pass evaluation behind fscore): counts EQUAL to
+the oracle's distances counted under the thresholds, scores the pinned float32
+arithmetic on them bit for bit, mean distances within rtol 1e-5.  Every case is
 run twice through the cached workspace with a call of another family (1e3-scale
 data) in between and must give the same bits; `generator` is repeated with x
 as a planes view.
@@ -20,6 +23,7 @@ import pytest
 import torch
 
 import dcd_restated as D
+import fscore_restated as FS
 import geometry_cases as G
 import kernel_loss_restated as K
 import knn_restated as KN
@@ -361,6 +365,74 @@ def test_dcd_counts_equal_and_values_within_bounds(cuda, oracle, entry, lam):
         zero = D.evaluate(np.zeros_like(d1), np.zeros_like(d2), i1, i2, alpha, lam, False)
         assert np.array_equal(zero["gd1"], res["gd1"])
         assert len(np.unique(gd1)) == 1 and len(np.unique(gd2)) == 1
+
+
+# ---------------------------------------------------------------------------
+# F-score: the one-pass Chamfer evaluation
+# ---------------------------------------------------------------------------
+def _fscore(c, cuda, rows=slice(None)):
+    """pcm_chamfer_eval on the case (or on `rows` of its batch) at the case's thresholds -> numpy
+    (mean_dist [B,2], counts [B,T,2], scores [B,T,3], batch [T,3])."""
+    import pcm_hip
+    x, y = _dev(cuda, c.x[rows], c.y[rows])
+    ths = G.fscore_thresholds(c)
+    b, t = x.shape[0], len(ths)
+    md = torch.full((b, 2), -7.0, device=cuda)
+    cn = torch.full((b, t, 2), -7, dtype=torch.int32, device=cuda)
+    sc = torch.full((b, t, 3), -7.0, device=cuda)
+    bs = torch.full((t, 3), -7.0, device=cuda)
+    pcm_hip.chamfer_eval(x, y, ths, md, cn, sc, bs)
+    torch.cuda.synchronize()
+    return md.cpu().numpy(), cn.cpu().numpy(), sc.cpu().numpy(), bs.cpu().numpy()
+
+
+def _fscore_check(family, shape, cuda, oracle):
+    c = G.case("fscore", family, shape)
+    if shape in G.SHAPES["fscore"]:
+        d1, d2 = G.fscore_forward(family, shape)
+    else:  # the one wide case: not kept
+        d1, d2, _, _ = oracle.chamfer_forward(c.x, c.y)
+    ths = G.fscore_thresholds(c)
+    n, m = c.x.shape[1], c.y.shape[1]
+    md, cn, sc, bs = first = _fscore(c, cuda)
+    _fscore(G.case("fscore", G.other_family("fscore", family), shape), cuda)  # through the cached workspace
+    for k, (a, b) in enumerate(zip(first, _fscore(c, cuda))):
+        assert np.array_equal(FS.bits(a), FS.bits(b)), (family, shape, "second run", k)
+    np.testing.assert_array_equal(cn[:, :, 0], FS.counts_from(d1, ths))
+    np.testing.assert_array_equal(cn[:, :, 1], FS.counts_from(d2, ths))
+    want = FS.scores_from(cn[:, :, 0], cn[:, :, 1], n, m)
+    np.testing.assert_array_equal(FS.bits(sc), FS.bits(want))
+    np.testing.assert_array_equal(FS.bits(bs), FS.bits(FS.batch_from(want)))
+    # rtol 1e-5 (167 x 2^-24) of the float64 mean: non-negative terms, chains of at most 6 DPP steps + 8 waves
+    # + 20 records (a workgroup per 128 or 256 queries) -- as tests/test_fscore_gpu.py derives it; where the
+    # quotient rounds in the subnormal range, half a subnormal's spacing more (2^-149 covers it)
+    ref = np.stack([d1.astype(np.float64).mean(1), d2.astype(np.float64).mean(1)], 1)
+    if family == "identical":
+        assert not md.any() and not ref.any()
+    _within("fscore", family, "mean_dist", md, ref, 1e-5 * ref + (2.0 ** -149 if family == "scale_1e-20" else 0.0))
+    return c, first
+
+
+@pytest.mark.parametrize("entry", G.entries("fscore"), ids=_ids("fscore"))
+def test_fscore_counts_equal_scores_bitwise_and_means_within_bound(cuda, oracle, entry):
+    _fscore_check(entry[0], entry[1], cuda, oracle)
+
+
+@pytest.mark.parametrize("family", ["centred", "offset_1000"])
+def test_fscore_four_queries_per_lane(cuda, oracle, family):
+    _fscore_check(family, G.FSCORE_WIDE_SHAPE, cuda, oracle)
+
+
+def test_fscore_subnormal_cloud_alone_equals_its_place_in_the_batch(cuda, oracle):
+    shape = G.SHAPES["fscore"][1]
+    c = G.case("fscore", "scale_1e-20", shape)
+    md, cn, sc, _ = _fscore(c, cuda)
+    md1, cn1, sc1, bs1 = _fscore(c, cuda, rows=slice(1, 2))
+    assert cn1[0, :3].min() > 0 and cn1[0, 0].max() < cn1[0, 2].min()  # the subnormal thresholds do count
+    np.testing.assert_array_equal(cn1[0], cn[1])
+    np.testing.assert_array_equal(FS.bits(md1[0]), FS.bits(md[1]))
+    np.testing.assert_array_equal(FS.bits(sc1[0]), FS.bits(sc[1]))
+    np.testing.assert_array_equal(FS.bits(bs1), FS.bits(sc[1]))  # a batch of one: its own scores
 
 
 # ---------------------------------------------------------------------------

@@ -27,64 +27,17 @@ import numpy as np
 import pytest
 import torch
 
+import silhouette_restated as R
+from silhouette_restated import FWD_ATOL, FWD_RTOL, U, _bce_f64, _factors, _pinned, grad_f64, sil_f64
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden", "silhouette_golden.npz")
 HEADER = os.path.join(REPO, "include", "pcm.h")
 
-FWD_RTOL, FWD_ATOL = 1e-4, 1e-30
-U = 2.0 ** -24
-
-
-# ---------------------------------------------------------------- references
-
-
-def _pinned(xyz, grid_h, grid_w):
-    """(gx, gy) of the contract's float32 co-ordinate map, widened to float64."""
-    x = np.asarray(xyz, np.float32)
-    gx = ((x[..., 0] + np.float32(1)) * np.float32(grid_h)) / np.float32(2)
-    gy = ((x[..., 1] + np.float32(1)) * np.float32(grid_w)) / np.float32(2)
-    assert gx.dtype == np.float32
-    return gx.astype(np.float64), gy.astype(np.float64)
-
-
-def _factors(g, cells, sigma_sq):
-    d = g[..., None] - np.arange(cells, dtype=np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        e = np.exp(-(d * d) / (2.0 * sigma_sq))
-    return d, e
-
-
-def sil_f64(xyz, grid_h, grid_w, sigma_sq):
-    gx, gy = _pinned(xyz, grid_h, grid_w)
-    _, ex = _factors(gx, grid_h, sigma_sq)
-    _, ey = _factors(gy, grid_w, sigma_sq)
-    return np.einsum("bnh,bnw->bhw", ex, ey)
-
-
-def grad_f64(xyz, G, grid_h, grid_w, sigma_sq):
-    """(gradient [B, N, 3], bound term A [B, N, 2]) by float64 autograd of the
-    restatement with respect to the pinned grid co-ordinates, times their
-    derivative grid / 2; A is the same sum over the absolute values of its terms."""
-    gx, gy = _pinned(xyz, grid_h, grid_w)
-    tx = torch.from_numpy(gx).requires_grad_()
-    ty = torch.from_numpy(gy).requires_grad_()
-    ex = torch.exp(-(tx[..., None] - torch.arange(grid_h, dtype=torch.float64)) ** 2 / (2.0 * sigma_sq))
-    ey = torch.exp(-(ty[..., None] - torch.arange(grid_w, dtype=torch.float64)) ** 2 / (2.0 * sigma_sq))
-    S = torch.einsum("bnh,bnw->bhw", ex, ey)
-    G64 = torch.from_numpy(np.asarray(G, np.float64))
-    S.backward(G64)
-    grad = np.zeros(gx.shape + (3,), np.float64)
-    grad[..., 0] = tx.grad.numpy() * (grid_h / 2.0)
-    grad[..., 1] = ty.grad.numpy() * (grid_w / 2.0)
-    dx, nex = _factors(gx, grid_h, sigma_sq)
-    dy, ney = _factors(gy, grid_w, sigma_sq)
-    aG = np.abs(np.asarray(G, np.float64))
-    A = np.zeros(gx.shape + (2,), np.float64)
-    A[..., 0] = np.einsum("bnh,bnw,bhw->bn", np.abs(dx / sigma_sq) * nex, ney, aG) * (grid_h / 2.0)
-    A[..., 1] = np.einsum("bnh,bnw,bhw->bn", nex, np.abs(dy / sigma_sq) * ney, aG) * (grid_w / 2.0)
-    return grad, A
+# the float64 references and the tolerance constants live in tests/silhouette_restated.py, shared with
+# tests/test_silhouette_edges_cpu.py and tests/test_silhouette_edges_gpu.py
 
 
 @functools.lru_cache(maxsize=None)
@@ -296,48 +249,77 @@ def _bce_chain():
     return int(re.search(r"#define\s+PCM_PROJ_BCE_CHAIN\s+(\d+)", src).group(1))
 
 
-def _bce_f64(pred, gt, w):
-    """(terms, gradient of their mean) in float64 from the float32-pinned a and c."""
-    pred = np.asarray(pred, np.float32)
-    a = pred + np.float32(1e-8)
-    q = (np.float32(1) - pred) - np.float32(1e-8)
-    cc = np.abs(q)
-    assert a.dtype == np.float32 and q.dtype == np.float32
-    a, q, cc, g = a.astype(np.float64), q.astype(np.float64), cc.astype(np.float64), np.asarray(gt, np.float64)
-    term = ((-g) * np.log(a)) * w - (1.0 - g) * np.log(cc)
-    count = float(np.float32(pred.size))
-    grad = (-g * w / a + (1.0 - g) / q) / count
-    return term, grad
+@pytest.mark.parametrize("w", [1.0, 0.5])
+@pytest.mark.parametrize("count", R.BCE_COUNTS + R.BCE_NEW_COUNTS)
+def test_proj_bce_loss_and_gradient(cuda, count, w):
+    # the new counts: the two sides of the single-workgroup switch (2048 / 2049), the last count whose
+    # partials fit one trip of the finalise kernel's strided loop (524288 = 256 workgroups), the first that
+    # takes a second (524289), 257 full workgroups, and 2^20, the largest count PCM_PROJ_BCE_CHAIN covers.
+    # gt = rand are probabilities; gt = rand * 3 are silhouette targets, above 1 where points overlap.
+    import pcm_hip
+    L = _bce_chain()
+    assert L <= 1024 and count <= 2 ** 20
+    for gt_scale in R.BCE_GT_SCALES:
+        pred, gt = R.bce_inputs(count, gt_scale)
+        term, grad = _bce_f64(pred.numpy(), gt.numpy(), w)
+        want = term.sum() / float(np.float32(count))
+        tol = (L + 8) * U * np.mean(np.abs(term)) + 2.4e-7
+        p, t = pred.to(cuda), gt.to(cuda)
+        loss = torch.full((1,), float("nan"), device=cuda)
+        gp = torch.full((count,), float("nan"), device=cuda)
+        pcm_hip.proj_bce(p, t, w, loss, gp)
+        got = float(loss.item())
+        print(f"count {count} w {w} gt x{gt_scale:g}: loss {got!r} want {want!r} |err| {abs(got - want):.3g} "
+              f"tol {tol:.3g} err/tol {abs(got - want) / tol:.3g}; "
+              f"grad max rel err {np.max(np.abs(gp.cpu().numpy() - grad) / np.abs(grad)):.3g}")
+        R.note("bce", count, gt_scale, abs(got - want) / tol)
+        assert abs(got - want) <= tol
+        np.testing.assert_allclose(gp.cpu().numpy().astype(np.float64), grad, rtol=1e-6, atol=0)
+        # grad_pred = NULL is accepted and leaves the loss bit for bit the same; so does a second run
+        loss2 = torch.full((1,), float("nan"), device=cuda)
+        pcm_hip.proj_bce(p, t, w, loss2, None)
+        assert _same_bits(loss, loss2)
+        gp2 = torch.empty_like(gp)
+        pcm_hip.proj_bce(p, t, w, loss2, gp2)
+        assert _same_bits(loss, loss2) and _same_bits(gp, gp2)
+        if count > 2048:  # more than one workgroup: the partials go through the workspace, whatever it held
+            need = pcm_hip.load_library().pcm_proj_bce_workspace_bytes(count)
+            assert need >= 4 * ((count + 2047) // 2048)
+            junk = torch.full((need,), 0xFF, dtype=torch.uint8, device=cuda)  # NaN bit patterns
+            for _ in range(2):
+                loss3 = torch.full((1,), float("nan"), device=cuda)
+                pcm_hip.proj_bce(p, t, w, loss3, None, workspace=junk)
+                assert _same_bits(loss, loss3)
 
 
 @pytest.mark.parametrize("w", [1.0, 0.5])
-@pytest.mark.parametrize("count", [1, 63, 4097, 32 * 64 * 64])
-def test_proj_bce_loss_and_gradient(cuda, count, w):
+def test_proj_bce_edge_values_per_element(cuda, w):
+    """R.bce_edge_vector, one element a call (count = 1: the loss is the element's term, the gradient its
+    derivative), so that a log(1e-8) term cannot hide its neighbours in a sum."""
     import pcm_hip
     L = _bce_chain()
-    assert L <= 1024
-    g = torch.Generator().manual_seed(41)
-    pred = torch.rand(count, generator=g) * 3
-    gt = torch.rand(count, generator=g)
-    term, grad = _bce_f64(pred.numpy(), gt.numpy(), w)
-    want = term.sum() / float(np.float32(count))
-    tol = (L + 8) * U * np.mean(np.abs(term)) + 2.4e-7
-    p, t = pred.to(cuda), gt.to(cuda)
+    preds, gts = R.bce_edge_vector()
+    assert preds.size == 28
+    term, _ = _bce_f64(preds, gts, w)
+    assert np.isfinite(term).all()
+    worst = 0.0
+    for k in range(preds.size):
+        want, grad = _bce_f64(preds[k:k + 1], gts[k:k + 1], w)
+        tol = (L + 8) * U * abs(want[0]) + 2.4e-7
+        loss = torch.full((1,), float("nan"), device=cuda)
+        gp = torch.full((1,), float("nan"), device=cuda)
+        p, t = torch.from_numpy(preds[k:k + 1]).to(cuda), torch.from_numpy(gts[k:k + 1]).to(cuda)
+        pcm_hip.proj_bce(p, t, w, loss, gp)
+        got, got_g = float(loss.item()), float(gp.item())
+        worst = max(worst, abs(got - want[0]) / tol)
+        assert abs(got - want[0]) <= tol, (preds[k], gts[k], got, want[0])
+        assert abs(got_g - grad[0]) <= 1e-6 * abs(grad[0]), (preds[k], gts[k], got_g, grad[0])
+    print(f"edge vector w {w}: worst |err| / tol {worst:.3g}")
+    # the whole vector in one call: the same terms through the workgroup's sum
+    want = term.sum() / float(np.float32(preds.size))
     loss = torch.full((1,), float("nan"), device=cuda)
-    gp = torch.full((count,), float("nan"), device=cuda)
-    pcm_hip.proj_bce(p, t, w, loss, gp)
-    got = float(loss.item())
-    print(f"count {count} w {w}: loss {got!r} want {want!r} |err| {abs(got - want):.3g} tol {tol:.3g}; "
-          f"grad max rel err {np.max(np.abs(gp.cpu().numpy() - grad) / np.abs(grad)):.3g}")
-    assert abs(got - want) <= tol
-    np.testing.assert_allclose(gp.cpu().numpy().astype(np.float64), grad, rtol=1e-6, atol=0)
-    # grad_pred = NULL is accepted and leaves the loss bit for bit the same; so does a second run
-    loss2 = torch.full((1,), float("nan"), device=cuda)
-    pcm_hip.proj_bce(p, t, w, loss2, None)
-    assert _same_bits(loss, loss2)
-    gp2 = torch.empty_like(gp)
-    pcm_hip.proj_bce(p, t, w, loss2, gp2)
-    assert _same_bits(loss, loss2) and _same_bits(gp, gp2)
+    pcm_hip.proj_bce(torch.from_numpy(preds).to(cuda), torch.from_numpy(gts).to(cuda), w, loss, None)
+    assert abs(float(loss.item()) - want) <= (L + 8) * U * np.mean(np.abs(term)) + 2.4e-7
 
 
 # ---------------------------------------------------------------- autograd
