@@ -38,6 +38,7 @@ EXPORTED = (
     "pcm_chamfer_backward_strided", "pcm_chamfer_loss_grad_layout", "pcm_chamfer_loss_grad_rescale",
     "pcm_chamfer_loss_grad_steps",
     "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
+    "pcm_chamfer_cross_workspace_bytes", "pcm_chamfer_cross",
     "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
     "pcm_fps",
     "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
@@ -241,6 +242,13 @@ def _open(path):
         L.pcm_dcd_workspace_bytes.argtypes = [ci, ci, ci]
         L.pcm_dcd_loss.restype = ci
         L.pcm_dcd_loss.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, cs, vp]
+    if hasattr(L, "pcm_chamfer_cross"):  # absent from A/B builds of older sources
+        L.pcm_chamfer_cross_workspace_bytes.restype = cs
+        L.pcm_chamfer_cross_workspace_bytes.argtypes = [ci, ci, ci, ci]
+        L.pcm_chamfer_cross.restype = ci
+        L.pcm_chamfer_cross.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, cs, vp]
+        L.pcm_tune_chamfer_cross_run.restype = ci
+        L.pcm_tune_chamfer_cross_run.argtypes = [ci, ci, ci, ci, ci]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1349,6 +1357,59 @@ def sliced_wasserstein_loss(xyz1, lay1, xyz2, lay2, dirs, loss_out, slices=None,
             _ptr(xyz1), _ptr(xyz2), b, n, m, int(lay1), int(lay2), _ptr(dirs), l, _ptr(loss_out), _ptr(slices),
             _ptr(gradxyz1), _ptr(gradxyz2), _ptr(order1), _ptr(order2), _ptr(workspace), workspace.numel(),
             _stream(dev)), "pcm_sliced_wasserstein_loss")
+
+
+CROSS_MAX_POINTS = 16384  # include/pcm.h PCM_CROSS_MAX_POINTS
+CROSS_QUERIES = 1024  # query points per workgroup of csrc/chamfer_cross.hip (kCrossQW: 4 waves x 64 lanes x 4)
+CROSS_TILE = 1024  # target points per LDS tile (kCrossTile)
+CROSS_J = 8  # target clouds a workgroup streams past its queries, at most (kCrossJ)
+CROSS_MIN_BLOCKS = 256  # the run is halved while the grid stays below this many workgroups (kCrossWantBlocks)
+
+
+def chamfer_cross_run(s: int, r: int, n: int, m: int, both_dirs: bool = True) -> int:
+    """Internal (tests): the target clouds per workgroup pcm_chamfer_cross takes
+    at this shape: CROSS_J, halved while the grid stays below CROSS_MIN_BLOCKS."""
+    return int(load_library().pcm_tune_chamfer_cross_run(int(s), int(r), int(n), int(m), int(bool(both_dirs))))
+
+
+def chamfer_cross_workspace_bytes(s: int, r: int, n: int, m: int) -> int:
+    return int(load_library().pcm_chamfer_cross_workspace_bytes(int(s), int(r), int(n), int(m)))
+
+
+def chamfer_cross_workspace(dev: torch.device, s: int, r: int, n: int, m: int) -> torch.Tensor:
+    """Scratch for chamfer_cross (a float64 record per entry, direction and
+    workgroup of a query cloud): ONE buffer per (device, current stream), grown
+    when a larger problem needs more; its content on entry is irrelevant and it
+    holds nothing between calls."""
+    need = max(chamfer_cross_workspace_bytes(s, r, n, m), 8)
+    key = ("cross", dev, _stream_id(dev))
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _cache_put(key, ws)
+    return _hand_out(ws)
+
+
+def chamfer_cross(xyz1, lay1, xyz2, lay2, mean12, mean21=None, workspace=None) -> None:
+    """pcm_chamfer_cross on the float32 cloud sets xyz1 [S, N, 3] and xyz2
+    [R, M, 3] (each rows, or a view of channel planes: layout 1): mean12 and,
+    when given, mean21 (contiguous float32 [S, R]) = the mean nearest-neighbour
+    squared distance of x_i's points to y_j and of y_j's points to x_i, both at
+    [i, j] (include/pcm.h).  At most two launches."""
+    outs = (mean12,) + (() if mean21 is None else (mean21,))
+    dev = _require_device(xyz1, xyz2, *outs)
+    _knn_cloud(xyz1, lay1, "chamfer_cross")
+    _knn_cloud(xyz2, lay2, "chamfer_cross")
+    s, n, r, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[0], xyz2.shape[1]
+    for t in outs:
+        if t.dtype != torch.float32 or tuple(t.shape) != (s, r) or not t.is_contiguous():
+            raise ValueError(f"an output must be contiguous float32 of shape {(s, r)}")
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = chamfer_cross_workspace(dev, s, r, n, m)
+        _check(load_library().pcm_chamfer_cross(
+            _ptr(xyz1), _ptr(xyz2), s, r, n, m, int(lay1), int(lay2), _ptr(mean12), _ptr(mean21), _ptr(workspace),
+            workspace.numel(), _stream(dev)), "pcm_chamfer_cross")
 
 
 DCD_MAX_POINTS = 16384  # include/pcm.h PCM_DCD_MAX_POINTS

@@ -308,6 +308,66 @@ int pcm_chamfer_eval_f16(const uint16_t *xyz1, const uint16_t *xyz2, int b, int 
                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Cross Chamfer matrix                                                    */
+/* ---------------------------------------------------------------------- */
+
+/* Largest cloud (points) pcm_chamfer_cross takes (else PCM_ERR_UNSUPPORTED). */
+#define PCM_CROSS_MAX_POINTS 16384
+
+/*
+ * Cross Chamfer matrix (extension): the mean nearest-neighbour squared distance
+ * of EVERY cloud of one set to EVERY cloud of another, both directions -- what
+ * nearest-shape retrieval, MMD-CD / COV-CD / 1-NNA-CD and duplicate checks
+ * between splits are functions of.  xyz1 holds s clouds of n points, xyz2 r
+ * clouds of m points.
+ * Values, both stored at [i, j] of an [s, r] matrix, so the caller's Chamfer
+ *   distance of (x_i, y_j) is their sum:
+ *     mean12[i, j] = (1/n) sum_p min_q d2(x_i[p], y_j[q])
+ *     mean21[i, j] = (1/m) sum_q min_p d2(x_i[p], y_j[q])
+ * Per-point arithmetic: d2 is the pinned fmaf(dz,dz,fmaf(dy,dy,dx*dx)) of
+ *   float32 differences; for finite input the per-point minimum is exactly the
+ *   dist1 / dist2 entry pcm_chamfer_forward gives for that pair of clouds (the
+ *   minimum of the pinned values is independent of the scan order: no argmin,
+ *   no rescan).
+ * Sums: a cloud's per-point minima are added in float64 in a fixed order (a
+ *   lane its queries ascending, a wave by the six DPP steps, the waves
+ *   ascending, then the cloud's workgroups ascending), divided by (double)n
+ *   (or m) and rounded ONCE to float32.  No float atomics.  Results are
+ *   bit-identical from run to run and across layouts, and entry (i, j) depends
+ *   on x_i and y_j alone: it equals the s = r = 1 call on those two clouds bit
+ *   for bit, wherever they stand in the sets.  The float64 accumulation keeps
+ *   the result within 1 ulp of float32(exact sum / n) whatever the order.
+ * mean21 == NULL skips that direction and changes no bit of mean12.
+ * layout1 / layout2: 0 = [., n, 3] rows, 1 = [., 3, n] channel planes; clouds
+ *   are read in place.
+ * Non-finite input: an entry whose cloud pair holds a non-finite coordinate is
+ *   unspecified but written; every other entry is unaffected, bit for bit; the
+ *   call always returns.
+ * Validation, before any device call: negative sizes or a layout outside
+ *   {0, 1} -> PCM_ERR_INVALID_ARG; then s == 0 or r == 0 is a no-op (PCM_OK,
+ *   also with null pointers); n == 0 or m == 0, a null cloud or a null mean12
+ *   -> PCM_ERR_INVALID_ARG; n or m above PCM_CROSS_MAX_POINTS, or s r or the
+ *   grid beyond the launch limits (2^31 - 1) -> PCM_ERR_UNSUPPORTED, nothing
+ *   launched; a workspace that is NULL or shorter than
+ *   pcm_chamfer_cross_workspace_bytes(s, r, n, m) -> PCM_ERR_WORKSPACE; one not
+ *   8-byte aligned -> PCM_ERR_INVALID_ARG.
+ * The workspace (one float64 record per entry, direction and workgroup of a
+ *   query cloud) needs no initialisation and keeps no state;
+ *   pcm_chamfer_cross_workspace_bytes is 0 for empty problems.
+ * Launches on `stream`: at most two -- the scan of both directions, then, only
+ *   if a cloud spans several workgroups (more than 1024 points), a finalise
+ *   that adds the partial records in ascending order (the hand-off is the
+ *   kernel boundary, as in pcm_chamfer_eval).  Capturable: no host
+ *   synchronisation, no allocation, nothing read back, no waiting between
+ *   workgroups.
+ */
+size_t pcm_chamfer_cross_workspace_bytes(int s, int r, int n, int m);
+int pcm_chamfer_cross(const float *xyz1 /* s clouds of n points */, const float *xyz2 /* r clouds of m points */,
+                      int s, int r, int n, int m, int layout1, int layout2,
+                      float *mean12 /* [s, r] */, float *mean21 /* NULL or [s, r] */,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Projection loss (finetune.py:154-162)                                   */
 /* ---------------------------------------------------------------------- */
 
