@@ -39,6 +39,7 @@ EXPORTED = (
     "pcm_chamfer_loss_grad_steps",
     "pcm_chamfer_eval_workspace_bytes", "pcm_chamfer_eval", "pcm_chamfer_eval_f16",
     "pcm_chamfer_cross_workspace_bytes", "pcm_chamfer_cross",
+    "pcm_chamfer_nd_forward", "pcm_chamfer_nd_backward",
     "pcm_silhouette_forward", "pcm_silhouette_backward", "pcm_proj_bce_workspace_bytes", "pcm_proj_bce",
     "pcm_fps",
     "pcm_knn", "pcm_repulsion_workspace_bytes", "pcm_repulsion_loss",
@@ -249,6 +250,13 @@ def _open(path):
         L.pcm_chamfer_cross.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, cs, vp]
         L.pcm_tune_chamfer_cross_run.restype = ci
         L.pcm_tune_chamfer_cross_run.argtypes = [ci, ci, ci, ci, ci]
+    if hasattr(L, "pcm_chamfer_nd_forward"):  # absent from A/B builds of older sources
+        L.pcm_chamfer_nd_forward.restype = ci
+        L.pcm_chamfer_nd_forward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+        L.pcm_chamfer_nd_backward.restype = ci
+        L.pcm_chamfer_nd_backward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        L.pcm_tune_chamfer_nd_geometry.restype = None
+        L.pcm_tune_chamfer_nd_geometry.argtypes = [vp, vp, vp]
     if hasattr(L, "pcm_tune_occupy"):  # absent from A/B builds of older sources
         L.pcm_tune_occupy.restype = ci
         L.pcm_tune_occupy.argtypes = [ci, ci, ci, ctypes.c_uint, vp]
@@ -1410,6 +1418,82 @@ def chamfer_cross(xyz1, lay1, xyz2, lay2, mean12, mean21=None, workspace=None) -
         _check(load_library().pcm_chamfer_cross(
             _ptr(xyz1), _ptr(xyz2), s, r, n, m, int(lay1), int(lay2), _ptr(mean12), _ptr(mean21), _ptr(workspace),
             workspace.numel(), _stream(dev)), "pcm_chamfer_cross")
+
+
+CHAMFER_ND_MAX_DIM = 8  # include/pcm.h PCM_CHAMFER_ND_MAX_DIM
+CHAMFER_ND_MAX_POINTS = 16384  # include/pcm.h PCM_CHAMFER_ND_MAX_POINTS
+CHAMFER_ND_TILE = 1024  # candidates per LDS tile of csrc/chamfer_nd.hip (kNdTile)
+CHAMFER_ND_QUERIES = 256  # queries per workgroup (kNdQB: 64 lanes x 4 a lane, held by every wave)
+CHAMFER_ND_WAVES = 8  # waves that share a tile, an eighth each (kNdW)
+
+
+def chamfer_nd_geometry():
+    """Internal (tests): (tile, queries per workgroup, waves a tile) as the loaded library was compiled."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    load_library().pcm_tune_chamfer_nd_geometry(*[ctypes.addressof(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def cloud_layout_nd(t: torch.Tensor):
+    """cloud_layout for a [B, N, D] cloud of any D >= 1: 0 for contiguous rows, 1 for
+    a [B, N, D] view of a contiguous [B, D, N] tensor (channel planes), None for
+    anything else.  A cloud that is both (D = 1 or N = 1) counts as rows."""
+    if t.dim() != 3 or t.shape[2] < 1:
+        return None
+    if t.is_contiguous():
+        return 0
+    return 1 if t.transpose(1, 2).is_contiguous() else None
+
+
+def _nd_clouds(x1, lay1, x2, lay2, what):
+    if x1.dim() != 3 or x2.dim() != 3 or x1.shape[0] != x2.shape[0] or x1.shape[2] != x2.shape[2]:
+        raise ValueError(f"{what} takes clouds [B, N, D] and [B, M, D] of one B and one D")
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32:
+        raise TypeError(f"{what} takes float32 clouds")
+    for t, lay in ((x1, lay1), (x2, lay2)):
+        # a cloud that is rows and planes at once (one point, one coordinate) passes as either
+        if lay not in (0, 1) or not (t.transpose(1, 2) if lay else t).is_contiguous():
+            raise ValueError(f"{what}: a cloud is not in layout {lay} (rows 0, a view of channel planes 1)")
+    b, n, d = x1.shape
+    return b, n, x2.shape[1], d
+
+
+def _nd_out(t, dtype, shape, what):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous {dtype} of shape {tuple(shape)}")
+
+
+def chamfer_nd_forward(x1, lay1, x2, lay2, dist1, dist2, idx1, idx2) -> None:
+    """pcm_chamfer_nd_forward on float32 clouds x1 [B, N, D] and x2 [B, M, D],
+    1 <= D <= CHAMFER_ND_MAX_DIM, each rows (0) or a view of channel planes (1,
+    cloud_layout_nd): dist float32 and idx int32, contiguous [B, N] / [B, M]."""
+    dev = _require_device(x1, x2, dist1, dist2, idx1, idx2)
+    b, n, m, d = _nd_clouds(x1, lay1, x2, lay2, "chamfer_nd_forward")
+    for t, dt, k in ((dist1, torch.float32, n), (dist2, torch.float32, m), (idx1, torch.int32, n),
+                     (idx2, torch.int32, m)):
+        _nd_out(t, dt, (b, k), "a chamfer_nd_forward output")
+    with torch.cuda.device(dev):
+        _check(load_library().pcm_chamfer_nd_forward(
+            _ptr(x1), _ptr(x2), b, n, m, d, int(lay1), int(lay2), _ptr(dist1), _ptr(dist2), _ptr(idx1), _ptr(idx2),
+            _stream(dev)), "pcm_chamfer_nd_forward")
+
+
+def chamfer_nd_backward(x1, lay1, x2, lay2, graddist1, graddist2, idx1, idx2, grad1, grad2) -> None:
+    """pcm_chamfer_nd_backward: grad1 / grad2 (float32, shaped and laid out as
+    their clouds) fully overwritten; graddists float32 and indices int32,
+    contiguous [B, N] / [B, M]."""
+    dev = _require_device(x1, x2, graddist1, graddist2, idx1, idx2, grad1, grad2)
+    b, n, m, d = _nd_clouds(x1, lay1, x2, lay2, "chamfer_nd_backward")
+    _nd_clouds(grad1, lay1, grad2, lay2, "chamfer_nd_backward (gradients)")
+    if tuple(grad1.shape) != tuple(x1.shape) or tuple(grad2.shape) != tuple(x2.shape):
+        raise ValueError("chamfer_nd_backward: a gradient is not shaped as its cloud")
+    for t, dt, k in ((graddist1, torch.float32, n), (graddist2, torch.float32, m), (idx1, torch.int32, n),
+                     (idx2, torch.int32, m)):
+        _nd_out(t, dt, (b, k), "a chamfer_nd_backward graddist / index")
+    with torch.cuda.device(dev):
+        _check(load_library().pcm_chamfer_nd_backward(
+            _ptr(x1), _ptr(x2), b, n, m, d, int(lay1), int(lay2), _ptr(graddist1), _ptr(graddist2), _ptr(idx1),
+            _ptr(idx2), _ptr(grad1), _ptr(grad2), _stream(dev)), "pcm_chamfer_nd_backward")
 
 
 DCD_MAX_POINTS = 16384  # include/pcm.h PCM_DCD_MAX_POINTS

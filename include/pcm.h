@@ -368,6 +368,71 @@ int pcm_chamfer_cross(const float *xyz1 /* s clouds of n points */, const float 
                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* N-D Chamfer distance (1 to 8 coordinates a point)                       */
+/* ---------------------------------------------------------------------- */
+
+/* Most coordinates a point may have (else PCM_ERR_UNSUPPORTED). */
+#define PCM_CHAMFER_ND_MAX_DIM 8
+/* Largest cloud (points) the N-D entries take (else PCM_ERR_UNSUPPORTED). */
+#define PCM_CHAMFER_ND_MAX_POINTS 16384
+
+/*
+ * N-D Chamfer distance (extension; upstream ChamferDistancePytorch ships
+ * chamfer2D / 3D / 5D / 6D): nearest neighbour with argmin in both directions,
+ * and a deterministic backward, for float32 clouds x1 [b, n, D] and
+ * x2 [b, m, D], 1 <= D = dim <= PCM_CHAMFER_ND_MAX_DIM.
+ * layout1 / layout2: 0 = contiguous rows [b, n, D], 1 = contiguous channel
+ *   planes [b, D, n]; clouds are read in place.
+ *
+ * Forward, direction 1 (direction 2 is the same with the roles swapped).  For
+ * query j and candidate k, every step in float32:
+ *     c_t = x2[k][t] - x1[j][t]
+ *     s   = c_0 * c_0                       (a rounded product)
+ *     s   = fmaf(c_t, c_t, s)               for t = 1 .. D-1
+ *   At D = 3 this is the library's pinned fmaf(dz,dz,fmaf(dy,dy,dx*dx)).
+ *     key_k    = s, or +inf if s is NaN
+ *     dist1[j] = min_k key_k
+ *     idx1[j]  = the lowest k with key_k == dist1[j]
+ *   So a NaN never wins; a query or candidate cloud that yields no finite key
+ *   gives (+inf, 0); ties go to the lowest index wherever the tied candidates
+ *   stand.  This is simpler than pcm_chamfer_forward's 512-point-tile NaN rule;
+ *   the two agree, bit for bit, on every input whose distances are all non-NaN.
+ *   m == 0 leaves dist1 / idx1 untouched and n == 0 leaves dist2 / idx2
+ *   untouched, as pcm_chamfer_forward does; b == 0 is a no-op.
+ *
+ * Backward: the order of pcm_chamfer_backward, per coordinate t.  With
+ * g = graddist * 2.f:
+ *     grad1[i] = ((+0 + direct) + s_j0) + s_j1 + ...   over the cloud-2 points
+ *                j with idx2[j] == i, ascending
+ *     grad2[k] = ((+0 + s_j0) + s_j1 + ...) + direct   over the cloud-1 points
+ *                j with idx1[j] == k, ascending, the direct term last
+ *     direct_t = g_self * (p_t - q_t),     p the point itself, q = other[idx_self]
+ *     s_j,t    = -(g_j * (p'_t - q_t)),    p' = other[j], q the point itself
+ *   Every operation is a separate float32 rounding; no float atomics: results
+ *   are bit-identical from run to run.  Gradients are fully overwritten and
+ *   written in their cloud's layout.  graddist1 [b, n], graddist2 [b, m],
+ *   idx1 [b, n] and idx2 [b, m] are contiguous.  n, m > 0 are required, and
+ *   every index must lie inside the cloud it points into (an index outside is
+ *   never followed, and the gradients it touches are unspecified).
+ *
+ * Validation, before any device call: negative sizes, dim < 1 or a layout
+ *   outside {0, 1} -> PCM_ERR_INVALID_ARG; dim > PCM_CHAMFER_ND_MAX_DIM or a
+ *   cloud above PCM_CHAMFER_ND_MAX_POINTS -> PCM_ERR_UNSUPPORTED; then b == 0
+ *   (forward: also n == 0 or m == 0) is a no-op (PCM_OK, also with null
+ *   pointers); backward with n == 0 or m == 0, or any null pointer ->
+ *   PCM_ERR_INVALID_ARG.
+ * Caller-owned buffers, no workspace, no allocation, no synchronisation; one
+ *   launch each on `stream`; capturable; no waiting between workgroups.
+ */
+int pcm_chamfer_nd_forward(const float *x1, const float *x2, int b, int n, int m, int dim,
+                           int layout1, int layout2, float *dist1, float *dist2,
+                           int32_t *idx1, int32_t *idx2, void *stream);
+int pcm_chamfer_nd_backward(const float *x1, const float *x2, int b, int n, int m, int dim,
+                            int layout1, int layout2, const float *graddist1, const float *graddist2,
+                            const int32_t *idx1, const int32_t *idx2,
+                            float *grad1, float *grad2, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Projection loss (finetune.py:154-162)                                   */
 /* ---------------------------------------------------------------------- */
 
